@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E: 8.0 TB/s spec
 
 
 def device_code_sha16():
@@ -62,6 +62,8 @@ def parse():
                     "(outside the timed region; the counters of ALL parts are compared whatever this says; 0 = no check)")
     ap.add_argument("--no-decompositions", action="store_true", help="skip the second decomposition (N = 1: the partition N >= 2 run; N >= 2: N = 1's partition)")
     ap.add_argument("--no-inclusive", action="store_true", help="skip the host-cycle-inclusive figure (repartition + moves + reassemble through the run driver)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one left in the parts (trees, log G, priors, counters) "
+                    "as DIR/<name>.npy in float32 / float64, at most 64 MB (a fixed, seeded sample of the part trees beyond that); N > 1: every rank its own parts, as rank<r>_<name>.npy")
     args = ap.parse_args()
     args.parts_auto = args.parts is None
     if args.parts is None:
@@ -354,6 +356,60 @@ def measure_resident(args, sc2, parts, moves, steps, world, rank, local_rank, sh
             "scaling": "strong", "per_rank": {"ms_per_step": rank_ms, "parts": rank_parts, "setup_s": rank_setup}, "parts_stopped_on_rank_0": bad}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+_TREE_FIELDS = ("parent", "child0", "child1", "t", "t_min", "t_max", "mut_offset", "mut_site", "mut_from", "mut_to", "mut_t",
+                "miss_offset", "miss_start", "miss_end", "mfs_offset", "mfs_site", "mfs_state")
+
+
+def dump_outputs(out_dir, eng, rank, world):
+    """--dump-outputs: what a caller of the timed pass receives from it, read back right after the last timed step (reads only:
+    the slabs are copied to the host, nothing on the device changes).  Per part, for every part of this rank: log G, augmented
+    coalescent prior, status, moves done, random draws, proposed / accepted per move kind.  The part trees themselves (every
+    array of the flat tree, parts concatenated in part order, part_* arrays to split them) for all parts when they fit in the
+    64 MB, else for a seeded sample of the parts.  Integers are written as float64 (int32) or float32 (uint8): exact."""
+    import numpy as np
+    b = eng.backend
+    n = eng.num_local_parts
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = "rank%d_" % rank if world > 1 else ""
+    trees = [b.part_download(p) for p in range(n)]
+    scal = {k: np.zeros(n) for k in ("part_log_G", "part_log_augmented_prior", "part_status", "part_moves_done", "part_rng_draws")}
+    scal["part_proposed"], scal["part_accepted"] = np.zeros((n, 5)), np.zeros((n, 5))
+    for p, t in enumerate(trees):
+        _, _, scal["part_log_G"][p], scal["part_log_augmented_prior"][p] = b.part_derived(p, t.num_nodes)
+        st = b.part_stats(p)
+        scal["part_status"][p], scal["part_moves_done"][p], scal["part_rng_draws"][p] = st["status"], st["moves_done"], st["rng_draws"]
+        scal["part_proposed"][p], scal["part_accepted"][p] = st["proposed"], st["accepted"]
+    scal["totals_log_G_log_augmented_prior"] = np.array(b.totals())
+    scal["part_ids"] = np.arange(eng.part_lo, eng.part_lo + n, dtype=np.float64)
+
+    def as_float(a):
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)
+
+    def tree_bytes(t):
+        return sum(as_float(getattr(t, f)).nbytes for f in _TREE_FIELDS) + 3 * 8
+    room = DUMP_LIMIT_BYTES - (64 << 10) - sum(a.nbytes for a in scal.values())     # (64 KB: the .npy headers)
+    sizes = [tree_bytes(t) for t in trees]
+    if sum(sizes) <= room:
+        chosen = list(range(n))
+    else:
+        chosen, used = [], 0
+        for p in np.random.default_rng(20261001).permutation(n):
+            if used + sizes[p] > room:
+                break
+            chosen.append(int(p)); used += sizes[p]
+        chosen.sort()
+    arrays = dict(scal)
+    arrays["tree_part_ids"] = np.array([eng.part_lo + p for p in chosen], np.float64)
+    arrays["tree_part_root"] = np.array([trees[p].root for p in chosen], np.float64)
+    arrays["tree_part_num_nodes"] = np.array([trees[p].num_nodes for p in chosen], np.float64)
+    for f in _TREE_FIELDS:
+        arrays["tree_" + f] = np.concatenate([as_float(getattr(trees[p], f)) for p in chosen]) if chosen else np.zeros(0)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values())), "parts": n, "parts_with_trees": len(chosen)}
+
+
 def _part_digest(backend, p):
     """What a part's chain left behind, as numbers that survive a float64 tensor: 48 bits of a hash of everything discrete (topology,
     sites, states, interval endpoints), the sum of its node times, its log G and augmented prior, its move and random-draw counts."""
@@ -508,6 +564,7 @@ def main():
         kernel_ms.append(None)
     barrier()
     dt = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, eng, rank, world) if args.dump_outputs else None
     # per-launch kernel time from HIP events on the engine's own stream (only the last launch's events survive
     # back-to-back launches, so re-time K launches one by one OUTSIDE the timed region for the roofline figure)
     ev_ms = []
@@ -712,6 +769,7 @@ def main():
             "mixing": mixing,
             "check": {"log_G": log_G, "log_augmented_coalescent_prior": log_prior, "parts_stopped": bad},
             "scale_check": check_scale,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(out))
     if world > 1:

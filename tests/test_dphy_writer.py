@@ -141,15 +141,8 @@ class Decoded:
 
 
 def test_the_schema_is_the_references():
-    """tests/golden/api_schema.json is what make_api_schema.py extracts from the reference's generated header (checked where the
-    reference is at hand), and it says what api.fbs says about a few fields one can read off the schema text."""
-    ref_hdr = "/root/reference/core/api_generated.h"
-    if os.path.exists(ref_hdr):
-        import subprocess, sys, tempfile, shutil
-        with tempfile.TemporaryDirectory() as tmp:
-            shutil.copy(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_api_schema.py"), tmp)
-            subprocess.run([sys.executable, os.path.join(tmp, "make_api_schema.py"), ref_hdr], check=True, capture_output=True)
-            assert json.load(open(os.path.join(tmp, "api_schema.json"))) == SCHEMA
+    """tests/golden/api_schema.json (what make_api_schema.py extracts from the reference's generated header, committed as data)
+    says what api.fbs says about a few fields one can read off the schema text."""
     P = SCHEMA["tables"]["Params"]["fields"]
     assert P["step"]["vt"] == 4 and P["mu_prior_alpha"]["vt"] == 4 + 2 * 38 and P["mu_prior_alpha"]["default"] == 1.0 and P["num_local_moves_per_global_move"]["default"] == -1
     assert P["pop_model"]["vt"] == 4 + 2 * 30 and P["pop_model_type"]["vt"] == 4 + 2 * 29 and P["mu_move_enabled"]["default"] == 1

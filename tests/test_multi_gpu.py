@@ -90,18 +90,28 @@ def _two_devices():
 @pytest.mark.parametrize("devices,exchange,cycles", [([0, 1], "rccl", 3), ([0, 1], "auto", 3), ([0, 1], "host", 3)])
 def test_shards_on_two_devices_equal_the_single_backend_run(devices, exchange, cycles):
     """The first test that runs ncclCommInitAll with n > 1 and the grouped ncclAllGather / ncclAllReduce BETWEEN devices
-    (emat_multi.cpp): collected on every box, skipped where there is one GPU (every lease so far), so that the first node with two runs
-    it by itself.  Same statement as above: every shard ends every cycle with exactly the single-backend tree; `auto` must have picked
-    RCCL (one shard per device), `host` exchanges the same records through host buffers."""
-    if not _two_devices():
-        pytest.skip("needs two GPUs (the test box has one)")
+    (emat_multi.cpp) where the box has two GPUs.  Same statement as above: every shard ends every cycle with exactly the
+    single-backend tree; `auto` must have picked RCCL (one shard per device), `host` exchanges the same records through host buffers.
+    Where the box has one GPU the two shards share it, and what the library must do then is checked instead: `host` and `auto` run the
+    same cycles through host buffers (`auto` must have seen that RCCL takes one rank per device), and `rccl` is refused outright rather
+    than run through host memory behind the caller's back."""
     sc = make_scenario("C3", num_tips=3000, num_sites=29903, uncertain_tips=0.1)
     parts, seed, moves = 128, 17, 400
+    if not _two_devices():
+        devices = [0, 0]
+    distinct = len(set(devices)) == len(devices)
+    if exchange == "rccl" and not distinct:
+        with pytest.raises(d.EmatError, match="INVALID_ARGUMENT"):
+            d.EmatMultiRun(devices, sc.tree, sc.ref, seed, exchange="rccl")
+        return
     want = _single(sc, parts, seed, cycles, moves)
     got, how = _multi(sc, devices, exchange, parts, seed, cycles, moves)
-    assert how.startswith("RCCL") == (exchange in ("rccl", "auto")), how
+    assert how.startswith("RCCL") == (exchange in ("rccl", "auto") and distinct), how
+    if not distinct:
+        assert "share a device" in how, how
     for c in range(cycles):
         (tree1, tot1), (trees, tot) = want[c], got[c]
+        assert len(trees) == 2
         for s, t in enumerate(trees):
             _same(t, tree1, "cycle %d shard %d" % (c, s))
         assert abs(tot[0] - tot1[0]) <= 1e-10 * abs(tot1[0]) and abs(tot[1] - tot1[1]) <= 1e-10 * abs(tot1[1]), (tot, tot1)
