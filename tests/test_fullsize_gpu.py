@@ -111,12 +111,22 @@ def test_trajectory_parity_at_c3_full_size():
     run_parity(sc, 400, 3000, seed=101, trace=3000)
 
 
-def test_trajectory_parity_on_the_benchmark_workload():
-    """The benchmark itself, checked move for move: config C4 (100 000 tips) cut exactly as bench.py cuts it, one pass of
-    1 000 moves on every one of the ~7 955 parts, each part's trace, tree, counters and RNG consumption against the oracle."""
+@pytest.mark.parametrize("max_part_nodes", [0, -1])
+def test_trajectory_parity_on_the_benchmark_workload(max_part_nodes):
+    """The benchmark itself, checked move for move: config C4 (100 000 tips) with 8 192 parts requested, one pass of 1 000 moves on
+    every part, each part's trace, tree, counters and RNG consumption against the oracle.  max_part_nodes = -1 is bench.py's own cut
+    (its --max-part-nodes default: parts larger than three times the mean get further cut nodes, 8 092 parts); 0 is the reference's
+    partitioning rule (7 955 parts)."""
     from helpers import run_parity
     sc = make_scenario("C4")
-    run_parity(sc, 8192, 1000, seed=20261001, trace=1000)
+    st = run_parity(sc, 8192, 1000, seed=20261001, trace=1000, max_part_nodes=max_part_nodes)
+    if max_part_nodes == -1:
+        eng = ShardedEngine(sc, num_parts=8192, seed=20261001, max_part_nodes=-1)      # how bench.py cuts the headline workload
+        try:
+            eng.repartition()
+            assert st["num_parts"] == eng.total_parts, (st["num_parts"], eng.total_parts)
+        finally:
+            eng.close()
 
 
 @pytest.mark.parametrize("num_parts,moves", [(8, 20000), (64, 5000)])
@@ -155,13 +165,14 @@ def test_c5_one_gpu_sampled_trajectories_and_whole_run_properties():
     try:
         configure(gpu, sc, ref, parts, incl, seeds, root_part)
         configure(orc, sc, ref, parts, incl, seeds, root_part)
+        sample = sorted(set(list(range(0, len(parts), 41)) + [root_part]))
+        cells = {p: orc.part_coalescent(p)["k_bar_p"].shape[0] for p in sample}      # compare_part's floor looks at grid growth
         gpu.run_moves_per_part(moves)
         gpu.synchronize()
-        sample = sorted(set(list(range(0, len(parts), 41)) + [root_part]))
         counts = np.zeros(len(parts), np.int64); counts[sample] = moves
         orc.run_moves_counts(counts, threads=8)
         for p in sample:
-            compare_part(gpu, orc, p, parts[p].num_nodes, moves, 1e-9, moves)
+            compare_part(gpu, orc, p, parts[p].num_nodes, moves, 1e-9, moves, grid_cells=cells[p])
         acc = np.zeros(5, np.int64)
         for p in range(len(parts)):
             st = gpu.part_stats(p)
