@@ -13,6 +13,11 @@ The SAME partition at every N (8192 parts requested, 7 955 obtained),
 sharded across ranks in contiguous blocks; the only cross-rank exchange is the per-cycle coalescent-grid all-reduce
 (<= a few KB) done before the timed region and a 2-double all-reduce of the log-posterior totals after it.
 Tree and partition are fixed as N grows => "scaling": "strong".
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.
+--full adds everything else the line can carry, each figure from runs of its own after the timed steps: the per-launch kernel
+time and roofline, the N > 1 self-check against one GPU (`scale_check`), the C5 series, the other decomposition, the CPU
+baseline, whole host-inclusive cycles and the committed posterior figures (`mixing`).
 """
 import argparse
 import json
@@ -50,18 +55,20 @@ def parse():
     ap.add_argument("--moves-per-part", type=int, default=None, help="moves per part and step; default 1000 on one GPU, and on N > 1 what keeps the moves of a step the same as on one GPU")
     ap.add_argument("--max-part-nodes", type=int, default=-1, help="not in the reference: parts larger than this get further, randomly drawn cut nodes at every repartition "
                                                                     "(-1 = the run driver's default, three times the mean part size; 0 = the reference's partitioning rule exactly)")
-    ap.add_argument("--secondary", default="C5", help="a second workload measured the same way and reported as `secondary` (default C5, the one with enough parts for eight GPUs; '' = none)")
-    ap.add_argument("--secondary-steps", type=int, default=3)
-    ap.add_argument("--inclusive-cycles", type=int, default=210, help="whole cycles of the `inclusive` figure (the reference redraws its partition stencils every 200 cycles)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure and check everything else the line can carry (the options below marked --full "
+                    "choose what); without it those fields of the line are null")
+    ap.add_argument("--secondary", default="C5", help="--full: a second workload measured the same way and reported as `secondary` (default C5, the one with enough parts for eight GPUs; '' = none)")
+    ap.add_argument("--secondary-steps", type=int, default=3, help="--full: timed steps of `secondary`")
+    ap.add_argument("--inclusive-cycles", type=int, default=210, help="--full: whole cycles of the `inclusive` figure (the reference redraws its partition stencils every 200 cycles)")
     ap.add_argument("--no-lds", action="store_true")
     ap.add_argument("--no-topology", action="store_true", help="diagnostic: disable subtree-slide and SPR moves")
     ap.add_argument("--only-displace", action="store_true", help="diagnostic: only inner-node displacement moves")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall-time budget of each CPU baseline sample")
-    ap.add_argument("--verify-parts", type=int, default=4, help="N > 1: parts per rank whose final trees are compared with a one-GPU run of the same partition on rank 0 "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: wall-time budget of each CPU baseline sample")
+    ap.add_argument("--verify-parts", type=int, default=4, help="--full, N > 1: parts per rank whose final trees are compared with a one-GPU run of the same partition on rank 0 "
                     "(outside the timed region; the counters of ALL parts are compared whatever this says; 0 = no check)")
-    ap.add_argument("--no-decompositions", action="store_true", help="skip the second decomposition (N = 1: the partition N >= 2 run; N >= 2: N = 1's partition)")
-    ap.add_argument("--no-inclusive", action="store_true", help="skip the host-cycle-inclusive figure (repartition + moves + reassemble through the run driver)")
+    ap.add_argument("--no-decompositions", action="store_true", help="--full: skip the second decomposition (N = 1: the partition N >= 2 run; N >= 2: N = 1's partition)")
+    ap.add_argument("--no-inclusive", action="store_true", help="--full: skip the host-cycle-inclusive figure (repartition + moves + reassemble through the run driver)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one left in the parts (trees, log G, priors, counters) "
                     "as DIR/<name>.npy in float32 / float64, at most 64 MB (a fixed, seeded sample of the part trees beyond that); N > 1: every rank its own parts, as rank<r>_<name>.npy")
     args = ap.parse_args()
@@ -484,6 +491,111 @@ def scale_check(args, sc, eng, passes, world, rank, shared_gpu, dist, torch):
     return out
 
 
+def roofline(args, eng, stats0, stats1, ev_ms, world, build_id):
+    """--full: roofline of the dominant kernel (k_run_moves) over the timed steps and the launches re-timed after them (`ev_ms`),
+    from the algorithmic bytes the kernel counts per executed move."""
+    import numpy as np
+    launches = args.steps + len(ev_ms)
+    # (of the parts that ran in that kernel: the few parts of the side classes run beside it in k_run_moves_side)
+    in_main = eng.backend.main_class_mask(eng.num_local_parts)
+    per_part = np.array(stats1["algorithmic_bytes_of_part"], np.float64) - np.array(stats0["algorithmic_bytes_of_part"], np.float64)
+    per_part_w = np.array(stats1["algorithmic_write_bytes_of_part"], np.float64) - np.array(stats0["algorithmic_write_bytes_of_part"], np.float64)
+    write_bytes_per_launch = float(per_part_w[in_main].sum()) / max(1, launches)
+    bytes_per_launch = float(per_part[in_main].sum()) / max(1, launches)
+    bytes_per_launch_all = float(per_part.sum()) / max(1, launches)
+    avg_ms = float(np.mean(ev_ms)) if ev_ms else float("nan")
+    achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    traffic, traffic_source, traffic_read, traffic_write = None, None, None, None
+    pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
+    # PMC counters cannot be read from inside this process: the figure comes from the committed rocprofv3 --pmc passes
+    # of this same command (scripts/profile.sh) and is stamped with the kernel build it was measured on; it is quoted
+    # only for the default single-GPU workload and only while the device code is the one that was profiled
+    if world == 1 and args.workload == "C4" and args.tips is None and args.parts == 8192 and args.moves_per_part == 1000 and args.max_part_nodes == -1 and not (args.no_topology or args.only_displace or args.no_lds):
+        try:
+            pm = json.load(open(pmc_path))
+            stamp = pm.get("device_code_sha16")
+            if stamp is None:
+                traffic_source = "unstamped: profiles/pmc_latest.json does not say which device code it was measured on"
+            elif stamp == build_id:
+                traffic = pm.get("hbm_bytes_per_launch")
+                # reads and writes apart: their sum can sit near the algorithmic bytes while each is far from its own share
+                # (the state lives in LDS: few reads; private frames of the topology moves: many writes)
+                if pm.get("FETCH_SIZE_KiB") is not None and pm.get("WRITE_SIZE_KiB") is not None:
+                    traffic_read, traffic_write = 2.0 * pm["FETCH_SIZE_KiB"] * 1024.0, pm["WRITE_SIZE_KiB"] * 1024.0
+                traffic_source = "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes on the library with emat_build_id %s)" % (pm.get("profile_dir", "pmc_latest.json"), stamp)
+            else:
+                traffic_source = "stale: profiles/pmc_latest.json was measured on device code %s, the loaded library is %s" % (stamp, build_id)
+        except Exception as e:
+            traffic, traffic_source = None, "unreadable profiles/pmc_latest.json: %s" % e
+    # "bound" names the yardstick the contract asks for; "limiter" says what actually limits the kernel (DESIGN.md section 5)
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_read": traffic_read, "traffic_write": traffic_write, "traffic_source": traffic_source,
+            "limiter": "instruction issue and LDS / L2 latency: a part's chain is serial and runs on one lane of its wavefront (the wave's other lanes "
+                       "take part in slab staging and in the candidate scan + study of SPR moves); residency is capped by LDS at 16 parts per CU",
+            "kernel": "k_run_moves", "kernel_ms": avg_ms, "algorithmic_bytes_per_launch": bytes_per_launch,
+            # reads and writes apart, each with its own denominator (VERDICT round 4): what the moves must read / must store, counted by the kernel
+            "algorithmic_read_bytes": bytes_per_launch - write_bytes_per_launch, "algorithmic_write_bytes": write_bytes_per_launch,
+            "traffic_read_over_algorithmic": (traffic_read / (bytes_per_launch - write_bytes_per_launch)) if traffic_read else None,
+            "traffic_write_over_algorithmic": (traffic_write / write_bytes_per_launch) if (traffic_write and write_bytes_per_launch > 0) else None,
+            "parts_in_kernel": int(in_main.sum()), "algorithmic_bytes_per_pass_all_parts": bytes_per_launch_all}
+
+
+def mixing_figures(build_id):
+    """--full: what the committed posterior runs say about mixing, quoted only while the device code is the one they ran on."""
+    # what a move buys: effective samples per second at the benchmark's part density next to the reference's few-part policy, from the
+    # committed posterior-equivalence run (scripts/posterior_check.py; a 500-tip tree, so its moves/s are not this workload's)
+    mixing = None
+    mix_path = os.path.join(ROOT, "profiles", "posterior_latest.json")
+    if os.path.exists(mix_path):
+        try:
+            pc = json.load(open(mix_path))
+            if pc.get("emat_build_id") != build_id:
+                raise KeyError("measured on device code %s, the loaded library is %s: not quoted (re-run scripts/posterior_check.py)" % (pc.get("emat_build_id"), build_id))
+            mixing = {"measured_on_emat_build_id": pc.get("emat_build_id"),
+                      "source": "profiles/posterior_latest.json (scripts/posterior_check.py: %d tips, %d retained samples per arm, one per cycle of 50 x nodes moves)" % (pc["tips"], pc["configs"][0]["retained"]),
+                      "worst_abs_z_between_arms": pc.get("worst_abs_z"),
+                      "arms": [{"parts": c["parts"], "frozen_fraction": c["frozen_fraction"], "moves_per_s": c["moves_per_s"],
+                                "ess_per_s": {k: v["ess_per_s"] for k, v in c["stats"].items()},
+                                "ess_per_million_moves": {k: v["ess_per_million_moves"] for k, v in c["stats"].items()}} for c in pc["configs"]]}
+        except Exception as e:
+            mixing = {"omitted": "profiles/posterior_latest.json: %s" % e}
+    # ... and at a size nearer the benchmark's (tests/posterior_scale.py: C3-like tree, 4 seeds; the coarse arm is the oracle with the
+    # reference's policy of 8 parts on 8 host threads, the fine arms run on the GPU): pooled z of the arms' means and ESS per second
+    scale_path = os.path.join(ROOT, "profiles", "posterior_scale_latest.json")
+    if os.path.exists(scale_path):
+        try:
+            ps = json.load(open(scale_path))
+            if ps.get("emat_build_id") != build_id:
+                raise KeyError("measured on device code %s, the loaded library is %s: not quoted (re-run tests/posterior_scale.py)" % (ps.get("emat_build_id"), build_id))
+            mixing = mixing or {}
+            mixing["at_scale"] = {"source": "profiles/posterior_scale_latest.json (tests/posterior_scale.py: %d tips, %d seeds, burn-in %d cycles)" % (ps["tips"], ps["seeds"], ps["burn_in"]),
+                                  "measured_on_emat_build_id": ps.get("emat_build_id"), "part_size_limit": ps.get("part_size_limit"),
+                                  "worst_abs_pooled_z": ps.get("worst_abs_pooled_z"),
+                                  # (every run of the comparison made on this round's code, not only the last one, and what they say together)
+                                  "replicates": ps.get("replicates"),
+                                  "pooled_z": {arm: {k: v["pooled_z"] for k, v in q.items()} for arm, q in ps.get("pooled", {}).items()},
+                                  "ess_per_s": {"gpu_at_benchmark_density": ps.get("ess_per_s_at_benchmark_density"), "oracle_8_parts_8_threads": ps.get("ess_per_s_reference_policy_oracle")}}
+        except Exception as e:
+            mixing = dict(mixing or {}, at_scale={"omitted": "profiles/posterior_scale_latest.json: %s" % e})
+
+    # ... and the run driver's part-size limit against the reference's partition rule, device arms only (tests/posterior_limit.py)
+    lim_path = os.path.join(ROOT, "profiles", "posterior_limit_latest.json")
+    if os.path.exists(lim_path):
+        try:
+            pl = json.load(open(lim_path))
+            if pl.get("emat_build_id") != build_id:
+                raise KeyError("measured on device code %s, the loaded library is %s: not quoted (re-run tests/posterior_limit.py)" % (pl.get("emat_build_id"), build_id))
+            mixing = mixing or {}
+            mixing["part_size_limit"] = {"source": "profiles/posterior_limit_latest.json (tests/posterior_limit.py: %d tips, %d parts requested, %d seeds, %d cycles, burn-in %d; every arm on the GPU, "
+                                                   "the arm under the reference's rule against the arms with the limit)" % (pl["tips"], pl["parts_requested"], pl["seeds"], pl["cycles"], pl["burn_in"]),
+                                         "measured_on_emat_build_id": pl.get("emat_build_id"), "worst_abs_pooled_z": pl.get("worst_abs_pooled_z"),
+                                         "arms": {arm: {"limit_in_effect": q.get("limit_in_effect"), "cut_nodes_added_per_cycle": q.get("cut_nodes_added_per_cycle"),
+                                                        "pooled_z": {k: v["pooled_z"] for k, v in q.items() if isinstance(v, dict)}} for arm, q in pl.get("pooled", {}).items()}}
+        except Exception as e:
+            mixing = dict(mixing or {}, part_size_limit={"omitted": "profiles/posterior_limit_latest.json: %s" % e})
+    return mixing
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -556,7 +668,7 @@ def main():
     for _ in range(args.warmup):
         eng.backend.run_moves_per_part(args.moves_per_part)
     barrier()
-    stats0 = eng.local_stats()
+    stats0 = eng.local_stats() if args.full else None     # (the roofline's algorithmic bytes are counted from here)
     kernel_ms = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -565,10 +677,10 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     dumped = dump_outputs(args.dump_outputs, eng, rank, world) if args.dump_outputs else None
-    # per-launch kernel time from HIP events on the engine's own stream (only the last launch's events survive
+    # --full: per-launch kernel time from HIP events on the engine's own stream (only the last launch's events survive
     # back-to-back launches, so re-time K launches one by one OUTSIDE the timed region for the roofline figure)
     ev_ms = []
-    for _ in range(min(args.steps, 3)):
+    for _ in range(min(args.steps, 3) if args.full else 0):
         eng.backend.run_moves_per_part(args.moves_per_part)
         eng.backend.synchronize()
         ev_ms.append(eng.backend.last_run_ms())
@@ -594,107 +706,24 @@ def main():
     value = moves_timed_all / dt
     log_G, log_prior = eng.global_totals()
     check_scale = None
-    if world > 1 and args.verify_parts > 0:
+    if args.full and world > 1 and args.verify_parts > 0:
         eng.backend_device = local_rank
         check_scale = scale_check(args, sc, eng, args.warmup + args.steps + len(ev_ms), world, rank, shared_gpu, dist, torch)
-
-    # roofline of the dominant kernel (k_run_moves): algorithmic bytes counted by the kernel per executed move
-    launches = args.steps + len(ev_ms)
-    # (of the parts that ran in that kernel: the few parts of the side classes run beside it in k_run_moves_side)
-    in_main = eng.backend.main_class_mask(eng.num_local_parts)
-    per_part = np.array(stats1["algorithmic_bytes_of_part"], np.float64) - np.array(stats0["algorithmic_bytes_of_part"], np.float64)
-    per_part_w = np.array(stats1["algorithmic_write_bytes_of_part"], np.float64) - np.array(stats0["algorithmic_write_bytes_of_part"], np.float64)
-    write_bytes_per_launch = float(per_part_w[in_main].sum()) / max(1, launches)
-    bytes_per_launch = float(per_part[in_main].sum()) / max(1, launches)
-    bytes_per_launch_all = float(per_part.sum()) / max(1, launches)
-    avg_ms = float(np.mean(ev_ms)) if ev_ms else float("nan")
-    achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    traffic, traffic_source, traffic_read, traffic_write = None, None, None, None
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
-    # PMC counters cannot be read from inside this process: the figure comes from the committed rocprofv3 --pmc passes
-    # of this same command (scripts/profile.sh) and is stamped with the kernel build it was measured on; it is quoted
-    # only for the default single-GPU workload and only while the device code is the one that was profiled
-    if world == 1 and args.workload == "C4" and args.tips is None and args.parts == 8192 and args.moves_per_part == 1000 and args.max_part_nodes == -1 and not (args.no_topology or args.only_displace or args.no_lds):
-        try:
-            pm = json.load(open(pmc_path))
-            stamp = pm.get("device_code_sha16")
-            if stamp is None:
-                traffic_source = "unstamped: profiles/pmc_latest.json does not say which device code it was measured on"
-            elif stamp == build_id:
-                traffic = pm.get("hbm_bytes_per_launch")
-                # reads and writes apart: their sum can sit near the algorithmic bytes while each is far from its own share
-                # (the state lives in LDS: few reads; private frames of the topology moves: many writes)
-                if pm.get("FETCH_SIZE_KiB") is not None and pm.get("WRITE_SIZE_KiB") is not None:
-                    traffic_read, traffic_write = 2.0 * pm["FETCH_SIZE_KiB"] * 1024.0, pm["WRITE_SIZE_KiB"] * 1024.0
-                traffic_source = "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes on the library with emat_build_id %s)" % (pm.get("profile_dir", "pmc_latest.json"), stamp)
-            else:
-                traffic_source = "stale: profiles/pmc_latest.json was measured on device code %s, the loaded library is %s" % (stamp, build_id)
-        except Exception as e:
-            traffic, traffic_source = None, "unreadable profiles/pmc_latest.json: %s" % e
+    roof = roofline(args, eng, stats0, stats1, ev_ms, world, build_id) if args.full else None
     bad = stats1["bad_parts"]
-    # what a move buys: effective samples per second at the benchmark's part density next to the reference's few-part policy, from the
-    # committed posterior-equivalence run (scripts/posterior_check.py; a 500-tip tree, so its moves/s are not this workload's)
-    mixing = None
-    mix_path = os.path.join(ROOT, "profiles", "posterior_latest.json")
-    if rank == 0 and os.path.exists(mix_path):
-        try:
-            pc = json.load(open(mix_path))
-            if pc.get("emat_build_id") != build_id:
-                raise KeyError("measured on device code %s, the loaded library is %s: not quoted (re-run scripts/posterior_check.py)" % (pc.get("emat_build_id"), build_id))
-            mixing = {"measured_on_emat_build_id": pc.get("emat_build_id"),
-                      "source": "profiles/posterior_latest.json (scripts/posterior_check.py: %d tips, %d retained samples per arm, one per cycle of 50 x nodes moves)" % (pc["tips"], pc["configs"][0]["retained"]),
-                      "worst_abs_z_between_arms": pc.get("worst_abs_z"),
-                      "arms": [{"parts": c["parts"], "frozen_fraction": c["frozen_fraction"], "moves_per_s": c["moves_per_s"],
-                                "ess_per_s": {k: v["ess_per_s"] for k, v in c["stats"].items()},
-                                "ess_per_million_moves": {k: v["ess_per_million_moves"] for k, v in c["stats"].items()}} for c in pc["configs"]]}
-        except Exception as e:
-            mixing = {"omitted": "profiles/posterior_latest.json: %s" % e}
-    # ... and at a size nearer the benchmark's (tests/posterior_scale.py: C3-like tree, 4 seeds; the coarse arm is the oracle with the
-    # reference's policy of 8 parts on 8 host threads, the fine arms run on the GPU): pooled z of the arms' means and ESS per second
-    scale_path = os.path.join(ROOT, "profiles", "posterior_scale_latest.json")
-    if rank == 0 and os.path.exists(scale_path):
-        try:
-            ps = json.load(open(scale_path))
-            if ps.get("emat_build_id") != build_id:
-                raise KeyError("measured on device code %s, the loaded library is %s: not quoted (re-run tests/posterior_scale.py)" % (ps.get("emat_build_id"), build_id))
-            mixing = mixing or {}
-            mixing["at_scale"] = {"source": "profiles/posterior_scale_latest.json (tests/posterior_scale.py: %d tips, %d seeds, burn-in %d cycles)" % (ps["tips"], ps["seeds"], ps["burn_in"]),
-                                  "measured_on_emat_build_id": ps.get("emat_build_id"), "part_size_limit": ps.get("part_size_limit"),
-                                  "worst_abs_pooled_z": ps.get("worst_abs_pooled_z"),
-                                  # (every run of the comparison made on this round's code, not only the last one, and what they say together)
-                                  "replicates": ps.get("replicates"),
-                                  "pooled_z": {arm: {k: v["pooled_z"] for k, v in q.items()} for arm, q in ps.get("pooled", {}).items()},
-                                  "ess_per_s": {"gpu_at_benchmark_density": ps.get("ess_per_s_at_benchmark_density"), "oracle_8_parts_8_threads": ps.get("ess_per_s_reference_policy_oracle")}}
-        except Exception as e:
-            mixing = dict(mixing or {}, at_scale={"omitted": "profiles/posterior_scale_latest.json: %s" % e})
-
-    # ... and the run driver's part-size limit against the reference's partition rule, device arms only (tests/posterior_limit.py)
-    lim_path = os.path.join(ROOT, "profiles", "posterior_limit_latest.json")
-    if rank == 0 and os.path.exists(lim_path):
-        try:
-            pl = json.load(open(lim_path))
-            if pl.get("emat_build_id") != build_id:
-                raise KeyError("measured on device code %s, the loaded library is %s: not quoted (re-run tests/posterior_limit.py)" % (pl.get("emat_build_id"), build_id))
-            mixing = mixing or {}
-            mixing["part_size_limit"] = {"source": "profiles/posterior_limit_latest.json (tests/posterior_limit.py: %d tips, %d parts requested, %d seeds, %d cycles, burn-in %d; every arm on the GPU, "
-                                                   "the arm under the reference's rule against the arms with the limit)" % (pl["tips"], pl["parts_requested"], pl["seeds"], pl["cycles"], pl["burn_in"]),
-                                         "measured_on_emat_build_id": pl.get("emat_build_id"), "worst_abs_pooled_z": pl.get("worst_abs_pooled_z"),
-                                         "arms": {arm: {"limit_in_effect": q.get("limit_in_effect"), "cut_nodes_added_per_cycle": q.get("cut_nodes_added_per_cycle"),
-                                                        "pooled_z": {k: v["pooled_z"] for k, v in q.items() if isinstance(v, dict)}} for arm, q in pl.get("pooled", {}).items()}}
-        except Exception as e:
-            mixing = dict(mixing or {}, part_size_limit={"omitted": "profiles/posterior_limit_latest.json: %s" % e})
+    mixing = mixing_figures(build_id) if args.full and rank == 0 else None
 
     # The same measurement on the workload that HAS the parts to fill eight GPUs (C5: 1 000 000 tips, about 80 000 parts -- the 100 000-tip
     # tree of the metric yields about 8 000, fewer than one GPU has wave slots from N = 2 on), so that a scaling run shows both curves.
     secondary = None
-    if args.secondary and args.secondary != args.workload and args.tips is None:
+    if args.full and args.secondary and args.secondary != args.workload and args.tips is None:
         secondary = measure_secondary(args, world, rank, local_rank, shared_gpu, allreduce, dist, torch)
 
     # Both decompositions side by side: `value` at N = 1 runs the 8192-part request, at N >= 2 the request grows with the GPUs and the moves per part
     # shrink so that a step keeps its moves.  A scaling curve read off `value` alone would mix the two: N = 1 therefore also times the grown partition, and N >= 2 the
     # fixed one, through the same timed region.
     decompositions = None
-    if args.parts_auto and args.moves_auto and args.workload == "C4" and args.tips is None and not args.no_decompositions:
+    if args.full and args.parts_auto and args.moves_auto and args.workload == "C4" and args.tips is None and not args.no_decompositions:
         step_moves = 1000.0 * base_parts
         if world == 1:
             decompositions = {"grown_partition": dict(measure_resident(args, sc, 8 * base_parts, 1000, args.steps, world, rank, local_rank, shared_gpu, allreduce, dist, torch, moves_of_a_step=step_moves),
@@ -708,12 +737,12 @@ def main():
                                                   "what": "the headline `value` of this line"}}
 
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_base = cpu_baseline(sc, args.parts, 20261001, args.cpu_seconds, eng.t_step)
     inclusive = None
-    if rank == 0 and world == 1 and not args.no_inclusive:
+    if args.full and rank == 0 and world == 1 and not args.no_inclusive:
         inclusive = inclusive_cycles(sc, args, args.inclusive_cycles)
-    if world > 1 and not args.no_inclusive:
+    if args.full and world > 1 and not args.no_inclusive:
         # whole sharded cycles: the reference's steps/s is inclusive of everything (tools/delphy.cpp:44-51; run.cpp:622-657), and so is this -- on both decompositions.
         # (The headline above is measured and stays whatever happens here: a failure of this section -- it has only ever run with all ranks on one GPU -- is reported
         # in the line instead of taking the line down; a failure that is not the same on every rank would still hang the collectives, which the launcher's timeout ends.)
@@ -750,24 +779,14 @@ def main():
                 "collectives": ("gloo on one shared GPU (plumbing check)" if shared_gpu else "RCCL, world size %d" % dist.get_world_size()) if world > 1 else "none (one rank)",
                 "emat_build_id": build_id,
             },
-            "per_rank": {"ms_per_step": rank_ms, "kernel_ms": rank_kernel_ms, "parts": rank_parts, "setup_s": rank_setup_s},
+            "per_rank": {"ms_per_step": rank_ms, "kernel_ms": rank_kernel_ms if ev_ms else None, "parts": rank_parts, "setup_s": rank_setup_s},
             "secondary": secondary,
             "decompositions": decompositions,
-            # "bound" names the yardstick the contract asks for; "limiter" says what actually limits the kernel
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_read": traffic_read, "traffic_write": traffic_write, "traffic_source": traffic_source,
-                         "limiter": "instruction issue and LDS / L2 latency: a part's chain is serial and runs on one lane of its wavefront (the wave's other lanes "
-                                    "take part in slab staging and in the candidate scan + study of SPR moves); residency is capped by LDS at 16 parts per CU",
-                         "kernel": "k_run_moves", "kernel_ms": avg_ms, "algorithmic_bytes_per_launch": bytes_per_launch,
-                         # reads and writes apart, each with its own denominator: what the moves must read / must store, counted by the kernel
-                         "algorithmic_read_bytes": bytes_per_launch - write_bytes_per_launch, "algorithmic_write_bytes": write_bytes_per_launch,
-                         "traffic_read_over_algorithmic": (traffic_read / (bytes_per_launch - write_bytes_per_launch)) if traffic_read else None,
-                         "traffic_write_over_algorithmic": (traffic_write / write_bytes_per_launch) if (traffic_write and write_bytes_per_launch > 0) else None,
-                         "parts_in_kernel": int(in_main.sum()), "algorithmic_bytes_per_pass_all_parts": bytes_per_launch_all},
+            "roofline": roof,
             "cpu_baseline": cpu_base,
             "inclusive": inclusive,
             "mixing": mixing,
-            "check": {"log_G": log_G, "log_augmented_coalescent_prior": log_prior, "parts_stopped": bad},
+            "check": {"log_G": log_G, "log_augmented_coalescent_prior": log_prior, "parts_stopped": bad, "after_passes": args.warmup + args.steps + len(ev_ms)},
             "scale_check": check_scale,
             "dumped_outputs": dumped,
         }

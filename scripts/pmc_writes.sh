@@ -3,7 +3,7 @@
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmcw_$TAG; mkdir -p $OUT; cd $GRAFT_REPO_ROOT
-B="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-inclusive --secondary="
+B="python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-inclusive --secondary="
 timeout 240 rocprofv3 --pmc TCC_EA_WRREQ_sum TCC_EA_WRREQ_64B_sum TCC_WRITE_sum TCC_WRITEBACK_sum --output-format csv -d $OUT/p1 -o p1 -- $B "$@" > $OUT/b1.log 2>&1
 timeout 240 rocprofv3 --pmc TCC_NORMAL_WRITEBACK_sum TCC_ALL_TC_OP_WB_WRITEBACK_sum TCC_NORMAL_EVICT_sum TCC_REQ_sum --output-format csv -d $OUT/p2 -o p2 -- $B "$@" > $OUT/b2.log 2>&1
 timeout 240 rocprofv3 --pmc TCP_TCC_WRITE_REQ_sum TCP_TCC_READ_REQ_sum TCP_TCC_ATOMIC_WITH_RET_REQ_sum TCP_TCC_ATOMIC_WITHOUT_RET_REQ_sum --output-format csv -d $OUT/p3 -o p3 -- $B "$@" > $OUT/b3.log 2>&1

@@ -1,9 +1,13 @@
 """bench.py --dump-outputs without a GPU: dump_outputs() over a stand-in backend writes every part's numbers and the part trees as
-float32 / float64 .npy files, exactly, and within its byte limit it keeps a seeded sample of the trees instead."""
+float32 / float64 .npy files, exactly, and within its byte limit it keeps a seeded sample of the trees instead.  On the GPU: a plain
+run (no --full) writes them beside the headline and measures nothing else."""
+import json
 import os
+import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -74,3 +78,23 @@ def test_dump_samples_the_trees_within_its_limit(tmp_path, monkeypatch):
     assert za.keys() == zb.keys() and all(np.array_equal(za[k], zb[k]) for k in za)        # the sample is fixed
     picked = [eng.backend.trees[i - 300] for i in ids]
     assert np.array_equal(za["rank1_tree_t"], np.concatenate([t.t for t in picked]))
+
+
+@pytest.mark.gpu
+def test_plain_run_writes_the_headline_and_its_outputs_only(tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` without --full: the headline and the arrays of the last timed step, none of
+    the figures --full measures (their fields are null), and no launch after the timed steps."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["unit"] == "moves/s" and out["higher_is_better"] is True and out["dtype"] == "f64" and out["steps"] == 2 and out["warmup"] == 1
+    assert all(out[k] is None for k in ("secondary", "decompositions", "roofline", "cpu_baseline", "inclusive", "mixing", "scale_check"))
+    assert out["per_rank"]["kernel_ms"] is None and out["check"]["parts_stopped"] == 0 and out["check"]["after_passes"] == 3
+    z = _load(str(tmp_path))
+    parts = z["part_ids"].shape[0]
+    assert out["dumped_outputs"]["files"] == len(z) and out["dumped_outputs"]["parts"] == parts > 7000
+    assert np.all(z["part_moves_done"] == 3000) and np.all(z["part_status"] == 0)
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - parts * 1000) < 1e-6 * parts * 1000          # value = the moves of a step / ms_per_step
+    assert np.allclose(z["totals_log_G_log_augmented_prior"], [out["check"]["log_G"], out["check"]["log_augmented_coalescent_prior"]], rtol=1e-12, atol=0)

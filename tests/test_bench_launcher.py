@@ -39,7 +39,7 @@ def test_two_ranks_on_the_one_gpu_of_the_test_box():
     """`python bench.py --gpus 2` as the driver would type it, on a one-GPU box (both ranks share cuda:0, collectives
     over gloo: the control flow of a 2-rank run, not RCCL): one JSON line, n_gpus 2, both ranks' parts and times."""
     import json
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--inclusive-cycles", "4", "--secondary", ""], {"EMAT_BENCH_SHARED_GPU": "1"})
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--inclusive-cycles", "4", "--secondary", ""], {"EMAT_BENCH_SHARED_GPU": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -69,7 +69,7 @@ def test_four_ranks_on_the_one_gpu_of_the_test_box():
     rank's setup, and carry the C5 series as `secondary`.  Four, not the driver's eight: with this test's own process, which holds the
     GPU too, eight ranks would be nine processes on one shared device, more than the six a test may keep open at once."""
     import json
-    r = _run(["--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-inclusive", "--secondary-steps", "1"], {"EMAT_BENCH_SHARED_GPU": "1"})
+    r = _run(["--gpus", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-inclusive", "--secondary-steps", "1"], {"EMAT_BENCH_SHARED_GPU": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 4 and len(out["per_rank"]["ms_per_step"]) == 4 and len(out["per_rank"]["setup_s"]) == 4 and max(out["per_rank"]["setup_s"]) < 120
@@ -87,7 +87,7 @@ def test_two_ranks_on_two_gpus_over_rccl():
     import json
     import torch
     n = torch.cuda.device_count()
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--secondary-steps", "1"], {})
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--secondary-steps", "1"], {})
     if n < 2:
         assert r.returncode != 0 and "bench.py --gpus 2: this node has %d GPU(s)" % n in r.stderr, r.stderr[-3000:]
         assert '"metric"' not in r.stdout and "local_rank" not in r.stderr and "rank 0 of 2" not in r.stderr
