@@ -24,16 +24,6 @@
 #include <stdexcept>
 
 #include "../../include/emat_backend.h"
-#ifdef EMAT_X_DIVERGENT
-__device__ __forceinline__ uint32_t emat_opaque_zero() { uint32_t z; asm("v_mov_b32 %0, 0" : "=v"(z)); return z; }
-#endif
-// 1: every lane of the wave runs the chain, all with the same values (the chain's code does not depend on the lane);
-// 0: lane 0 alone.  With one lane active every non-leaf device function saves and restores the INACTIVE lanes of the
-// VGPR it parks its return address in (s_xor_saveexec + scratch_store / scratch_load + s_waitcnt vmcnt(0)); with all
-// lanes active that save has nothing to store.
-#ifndef EMAT_CHAIN_ON_ALL_LANES
-#define EMAT_CHAIN_ON_ALL_LANES 0
-#endif
 #if defined(EMAT_PROFILE_PHASES) || defined(EMAT_COUNT_CALLS)
 namespace emat {
 constexpr int k_fn_replicas = 64;                          // (one table per workgroup index mod 64: eight thousand waves adding to ONE word per scope made the profiling build 5.6 x slower than the real one)
@@ -147,7 +137,7 @@ template <class CtxT> __device__ inline void init_ctx(CtxT& c, uint8_t* slab, ui
   c.only_displacing_inner_nodes = a.flags.only_displacing_inner_nodes != 0;
   c.topology_moves_enabled = a.flags.topology_moves_enabled != 0;
   c.includes_run_root = (c.H->flags & k_flag_includes_run_root) != 0;
-  c.rng_key = c.H->rng_key; c.rng_ctr = c.H->rng_counter; c.rng_spare = c.H->rng_spare; c.rng_has_spare = c.H->rng_has_spare != 0; c.rng_short = false; c.phase = 0; c.svc = 0; c.frame = nullptr;
+  c.rng_key = c.H->rng_key; c.rng_ctr = c.H->rng_counter; c.rng_spare = c.H->rng_spare; c.rng_has_spare = c.H->rng_has_spare != 0; c.phase = 0; c.svc = 0; c.frame = nullptr;
   c.rng_base = c.rng_ctr - (uint64_t)k_rng_blocks;   // nothing computed ahead yet: the chain's first step asks the wave for it
   c.mu_prop = 0.0; c.sc_top = c.H->scratch_begin; c.A = nullptr; c.a_top = 0; c.a_end = 0; c.failed = false; c.bytes = 0; c.bytes_w = 0;
   c.tr_kind = -1.0; c.tr_node = -1.0; c.tr_acc = 0.0; c.tr_log_mh = 0.0;
@@ -209,8 +199,9 @@ template <bool kSide> __device__ __forceinline__ void run_moves_body(const Kerne
   auto ld_ticks = [&]() -> int64_t { return __hip_atomic_load(&a.part_ticks[part], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
   uint8_t* gslab = a.slabs + a.slab_off[part];
   SlabHeader* gh = (SlabHeader*)gslab;
-#ifndef EMAT_X_DYN_LDS_BY_TABLE
-  // the staged variants address the dynamic LDS block at a constant (k_lds_dyn_base, emat_device_core.hpp): is it where they think it is?
+#if !defined(EMAT_PROFILE_PHASES) && !defined(EMAT_COUNT_CALLS)
+  // the staged variants address the dynamic LDS block at a constant (k_lds_dyn_base, emat_device_core.hpp; the profiling and
+  // call-counting builds take the symbol instead): is it where they think it is?
   if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)emat_lds != k_lds_dyn_base) {
     if (lane == 0) { gh->fail_line = -3; st_status(k_part_internal); if (a.chunks > 1) __hip_atomic_store(&a.chunk_done[part], a.chunks, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
     return;
@@ -322,10 +313,10 @@ template <bool kSide> __device__ __forceinline__ void run_moves_body(const Kerne
     // The chain: stretches of moves on lane 0; whenever a move parks itself for work the whole wave shares (the candidate
     // scan and study of an SPR move), all 64 lanes do that work and lane 0 picks the move up again.
     for (;;) {
-      if (EMAT_CHAIN_ON_ALL_LANES || lane == 0) {
-        if (staged) dev_lds::run_chain_loop(*(dev_lds::Ctx*)(emat_lds_ctx + EMAT_OPQ));
-        else if (prefix) dev_mix::run_chain_loop(*(dev_mix::Ctx*)(emat_lds_ctx + EMAT_OPQ));
-        else dev::run_chain_loop(*(dev::Ctx*)(emat_lds_ctx + EMAT_OPQ));
+      if (lane == 0) {
+        if (staged) dev_lds::run_chain_loop(*(dev_lds::Ctx*)(emat_lds_ctx));
+        else if (prefix) dev_mix::run_chain_loop(*(dev_mix::Ctx*)(emat_lds_ctx));
+        else dev::run_chain_loop(*(dev::Ctx*)(emat_lds_ctx));
       }
       __syncthreads();
       const int svc = ((const dev::Ctx*)(emat_lds_ctx))->svc;

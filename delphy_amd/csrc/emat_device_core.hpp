@@ -71,10 +71,7 @@ constexpr uint32_t k_lds_dyn_base = k_lds_tables_bytes + k_lds_ctx_bytes + (k_rn
 }  // namespace emat
 // Profiling and call-counting builds declare one more static LDS object (s_fn_count_me, emat_backend.hip): the dynamic block then does not
 // start at the constant, and run_moves_body's check would stop every part (fail_line -3).  Those builds take the symbol instead.
-#if (defined(EMAT_PROFILE_PHASES) || defined(EMAT_COUNT_CALLS)) && !defined(EMAT_X_DYN_LDS_BY_TABLE)
-#define EMAT_X_DYN_LDS_BY_TABLE
-#endif
-#ifdef EMAT_X_DYN_LDS_BY_TABLE   // (A/B: the symbol, as until round 5)
+#if defined(EMAT_PROFILE_PHASES) || defined(EMAT_COUNT_CALLS)
 #define EMAT_DYN_LDS ::emat::emat_lds
 #else
 #define EMAT_DYN_LDS ((uint8_t*)(__attribute__((address_space(3))) uint8_t*)(uintptr_t)::emat::k_lds_dyn_base)
@@ -85,89 +82,11 @@ constexpr uint32_t k_lds_dyn_base = k_lds_tables_bytes + k_lds_ctx_bytes + (k_rn
 // A function whose calls must not be marked as tail calls: its callees then qualify for LLVM's no-callee-saved-registers
 // optimisation.  The top of the call tree carries it; below, calls keep the standard convention.
 #define EMAT_NOTAIL __attribute__((disable_tail_calls))
-// Thirteen functions of the topology moves are INLINED at their call sites since round 6 (-DEMAT_OUTL_<TAG> puts one back out of line for an A/B); two large
-// ones stay out of line (-DEMAT_INL_<TAG> inlines one).  Measured one at a time and in combination at C4: KTP / SST -- the
-// K-truncated Poisson draw and the trajectory of one site, three rejection rounds per constrained site -- + 1.2 % of a pass together; HOP / SLIDE -- tree_editing's
-// hop and slide, once per level an SPR climbs -- + 0.5 % and + 0.3 %; FINI, PNIG, PEEL, PICKT, ADJ (finish_inner_graft_analysis, propose_new_inner_graft_mutations,
-// peel_inner_graft, study_pick_time_in_region, adjust_mutational_history) +- 0.1 % each and together; with SMH, SUMM, APPLY, LALPHA (sample_mutational_history,
-// summarize_closed_mutations, apply_inner_graft, study_log_alpha_in_region: - 0.2 ... - 0.5 % each ALONE) + 1.2 % all nine together -- what a call costs depends on what
-// else is out of line around it.  START (start_inner_graft_analysis, four call sites) - 0.8 %, TOPO (spr_move_topology) - 0.4 %: they stay calls; so do the leaf helpers sd_push_back_v,
-// find_MRCA_of, reconstruct_missing_sites_at, calc_site_state_at and edit_flip (- 0.1 ... - 0.5 % each inlined).
-#ifdef EMAT_OUTL_KTP
-#define EMAT_FN_KTP EMAT_DN
-#else
-#define EMAT_FN_KTP EMAT_DF
-#endif
-#ifdef EMAT_OUTL_SST
-#define EMAT_FN_SST EMAT_DN
-#else
-#define EMAT_FN_SST EMAT_DF
-#endif
-#ifdef EMAT_OUTL_HOP
-#define EMAT_FN_HOP EMAT_DN
-#else
-#define EMAT_FN_HOP EMAT_DF
-#endif
-#ifdef EMAT_OUTL_SLIDE
-#define EMAT_FN_SLIDE EMAT_DN
-#else
-#define EMAT_FN_SLIDE EMAT_DF
-#endif
-#ifdef EMAT_OUTL_FINI
-#define EMAT_FN_FINI EMAT_DN
-#else
-#define EMAT_FN_FINI EMAT_DF
-#endif
-#ifdef EMAT_OUTL_PNIG
-#define EMAT_FN_PNIG EMAT_DN
-#else
-#define EMAT_FN_PNIG EMAT_DF
-#endif
-#ifdef EMAT_OUTL_PEEL
-#define EMAT_FN_PEEL EMAT_DN
-#else
-#define EMAT_FN_PEEL EMAT_DF
-#endif
-#ifdef EMAT_OUTL_PICKT
-#define EMAT_FN_PICKT EMAT_DN
-#else
-#define EMAT_FN_PICKT EMAT_DF
-#endif
-#ifdef EMAT_OUTL_ADJ
-#define EMAT_FN_ADJ EMAT_DN
-#else
-#define EMAT_FN_ADJ EMAT_DF
-#endif
-#ifdef EMAT_OUTL_SMH
-#define EMAT_FN_SMH EMAT_DN
-#else
-#define EMAT_FN_SMH EMAT_DF
-#endif
-#ifdef EMAT_OUTL_SUMM
-#define EMAT_FN_SUMM EMAT_DN
-#else
-#define EMAT_FN_SUMM EMAT_DF
-#endif
-#ifdef EMAT_OUTL_APPLY
-#define EMAT_FN_APPLY EMAT_DN
-#else
-#define EMAT_FN_APPLY EMAT_DF
-#endif
-#ifdef EMAT_OUTL_LALPHA
-#define EMAT_FN_LALPHA EMAT_DN
-#else
-#define EMAT_FN_LALPHA EMAT_DF
-#endif
-#ifdef EMAT_INL_START
-#define EMAT_FN_START EMAT_DF
-#else
-#define EMAT_FN_START EMAT_DN
-#endif
-#ifdef EMAT_INL_TOPO
-#define EMAT_FN_TOPO EMAT_DF
-#else
-#define EMAT_FN_TOPO EMAT_DN
-#endif
+// Thirteen functions of the topology moves are inlined at their call sites (EMAT_DF): ktp_sample_s, sample_site_trajectory_v,
+// edit_do_hop_up, edit_slide_P_along_branch_v and nine graft and study steps -- the nine pay only together: what a call costs
+// depends on what else is out of line around it.  start_inner_graft_analysis (four call sites) and spr_move_topology stay calls
+// (EMAT_DN), as do the leaf helpers sd_push_back_v, find_MRCA_of, reconstruct_missing_sites_at, calc_site_state_at and edit_flip:
+// each was slower inlined.  Measured at C4 one at a time and in combination: DESIGN.md section 8, round 6.
 // -DEMAT_COUNT_CALLS: scripts/count_calls.py puts EMAT_CALLED(header) at the top of every device function of a copy of these
 // headers; calls are counted per (header, line) in g_fn_ticks[..][1] and read with emat_debug_fn_ticks.
 #ifdef EMAT_COUNT_CALLS
@@ -233,7 +152,6 @@ struct Ctx {
   uint32_t sc_top;            // HBM arena bump pointer (byte offset from G)
   bool failed;
   bool mv_rng_had_spare;      // RNG position at the first draw of the current move: (mv_rng_ctr, mv_rng_had_spare), see stop_for_cells
-  bool rng_short;             // a LEAF move asked for a number beyond what the wave has computed ahead (rng_next64_t<true>): it commits nothing and is run again out of line
   // statistics
   int64_t bytes;
   int64_t bytes_w;            // the part of `bytes` that is written (cells, re-timed lists, region records, re-hung nodes): roofline.algorithmic_write_bytes
@@ -247,18 +165,10 @@ struct Ctx {
 
 static_assert(sizeof(Ctx) + 16 <= k_lds_ctx_bytes, "context outgrew its LDS slot (the last 16 bytes are the kernel's flag word)");
 // Base pointers of the part's persistent state.
-// -DEMAT_X_DIVERGENT (an experiment): what the chain would cost if its addresses were NOT wave-uniform,
-// as they would be with several chains side by side in one wavefront -- every base address gets a zero the compiler cannot see
-// through (a VGPR), so address arithmetic, loaded values and branches all leave the scalar unit.  Still one chain per wave.
-#ifdef EMAT_X_DIVERGENT
-#define EMAT_OPQ ::emat_opaque_zero()   // (defined before the first inclusion, in emat_backend.hip)
-#else
-#define EMAT_OPQ 0u
-#endif
 #if EMAT_VARIANT_LDS
-EMAT_DF uint8_t* slab_at(const Ctx&, uint32_t off) { return EMAT_DYN_LDS + (off - (uint32_t)sizeof(SlabHeader)) + EMAT_OPQ; }   // slab byte `off` (beyond the header)
-EMAT_DF SlabHeader* hdr_of(const Ctx&) { return (SlabHeader*)(emat_lds_hdr + EMAT_OPQ); }
-EMAT_DF NodeRec* nodes_of(const Ctx&) { return (NodeRec*)(EMAT_DYN_LDS + EMAT_OPQ); }   // off_nodes == sizeof(SlabHeader), checked at launch
+EMAT_DF uint8_t* slab_at(const Ctx&, uint32_t off) { return EMAT_DYN_LDS + (off - (uint32_t)sizeof(SlabHeader)); }   // slab byte `off` (beyond the header)
+EMAT_DF SlabHeader* hdr_of(const Ctx&) { return (SlabHeader*)emat_lds_hdr; }
+EMAT_DF NodeRec* nodes_of(const Ctx&) { return (NodeRec*)EMAT_DYN_LDS; }   // off_nodes == sizeof(SlabHeader), checked at launch
 EMAT_DF const double* mu_of(const Ctx&) { return (const double*)emat_lds_tables; }
 EMAT_DF const double* pi_of(const Ctx&) { return (const double*)emat_lds_tables + k_max_lds_partitions; }
 EMAT_DF const double* q_of(const Ctx&) { return (const double*)emat_lds_tables + k_max_lds_partitions * 5; }
@@ -286,11 +196,6 @@ EMAT_D void fail_at(Ctx& c, int status, int line) {
 #ifdef EMAT_PROFILE_PHASES
 #define EMAT_SITE(line, hbm, v) atomicAdd(&::emat::g_arena_site_bytes[(line) & 2047][(hbm) ? 1 : 0], (unsigned long long)(v))
 #define EMAT_COUNT(c, k, v) (((int64_t*)hdr_of(c)->reserved)[k] += (int64_t)(v))
-#ifdef EMAT_X_UNLIMITED_SCANS   // probe variant: reserved[11], [12] count the scans without a limit and their ticks instead
-#define EMAT_COUNT_TRIMS(c, k, v) do {} while (0)
-#else
-#define EMAT_COUNT_TRIMS(c, k, v) EMAT_COUNT(c, k, v)
-#endif
 #define EMAT_PHASE_BEGIN() long long _ph_t0 = clock64()
 #define EMAT_PHASE(c, k) do { long long _t = clock64(); hdr_of(c)->phase_ticks[k] += _t - _ph_t0; _ph_t0 = _t; } while (0)
 #define EMAT_TIMED(file_id) ::emat::FnTimer _fn_timer((file_id) * 2048 + (__LINE__ & 2047))
@@ -303,7 +208,6 @@ EMAT_D void fail_at(Ctx& c, int status, int line) {
 #define EMAT_TIMED_END(name) do {} while (0)
 #define EMAT_SITE(line, hbm, v) do {} while (0)
 #define EMAT_COUNT(c, k, v) do {} while (0)
-#define EMAT_COUNT_TRIMS(c, k, v) do {} while (0)
 #define EMAT_PHASE_BEGIN() do {} while (0)
 #define EMAT_PHASE(c, k) do {} while (0)
 #endif
@@ -313,40 +217,10 @@ EMAT_D void fail_at(Ctx& c, int status, int line) {
 // site, and the instruction cache of a CU pair is 64 KB for 32 resident chains that are all somewhere else in the code
 // (measured: simple moves 15 % smaller, +1.5 % moves/s; taking the ten Philox rounds out of line as well costs more in
 // calls than it saves in fetches).
-#ifndef EMAT_INLINE_TRANSC   // bit mask: 1 log, 2 exp, 4 log1p, 8 expm1 inlined at their call sites instead of behind a call
-#define EMAT_INLINE_TRANSC 0
-#endif
-#ifdef EMAT_X_FLOAT_TRANSC   // (experiment: what the chain would gain if the four cost a third -- single precision; parity is gone)
-EMAT_DN double m_log(double x) { return (double)::logf((float)x); }
-EMAT_DN double m_exp(double x) { return (double)::expf((float)x); }
-EMAT_DN double m_log1p(double x) { return (double)::log1pf((float)x); }
-EMAT_DN double m_expm1(double x) { return (double)::expm1f((float)x); }
-#define EMAT_TRANSC_DEFINED
-#endif
-#ifdef EMAT_TRANSC_DEFINED
-#elif EMAT_INLINE_TRANSC & 1
-EMAT_DF double m_log(double x) { return ::log(x); }
-#else
 EMAT_DN double m_log(double x) { return ::log(x); }
-#endif
-#ifdef EMAT_TRANSC_DEFINED
-#elif EMAT_INLINE_TRANSC & 2
-EMAT_DF double m_exp(double x) { return ::exp(x); }
-#else
 EMAT_DN double m_exp(double x) { return ::exp(x); }
-#endif
-#ifdef EMAT_TRANSC_DEFINED
-#elif EMAT_INLINE_TRANSC & 4
-EMAT_DF double m_log1p(double x) { return ::log1p(x); }
-#else
 EMAT_DN double m_log1p(double x) { return ::log1p(x); }
-#endif
-#ifdef EMAT_TRANSC_DEFINED
-#elif EMAT_INLINE_TRANSC & 8
-EMAT_DF double m_expm1(double x) { return ::expm1(x); }
-#else
 EMAT_DN double m_expm1(double x) { return ::expm1(x); }
-#endif
 // ---- RNG: identical stream to the parity oracle (oracle/orc_core.hpp `Rng`) -------------------------
 EMAT_D void philox4x32_10(uint64_t ctr, uint64_t key, uint32_t out[4]) {
   uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0, c3 = 0;
@@ -369,11 +243,7 @@ EMAT_DN uint64_t rng_next64_computed(Ctx& c) {
   c.rng_spare = (uint64_t)w[2] | ((uint64_t)w[3] << 32); c.rng_has_spare = true;
   return (uint64_t)w[0] | ((uint64_t)w[1] << 32);
 }
-// kLeaf: for a move compiled as a LEAF function (no call anywhere in it: no return address to park, hence no whole-wave save and reload around every
-// move -- DESIGN.md section 8, round 6).  Its draws come from what the wave computed ahead; should that run out in the middle of the move (a long run
-// of rejected node picks: about one move in 10^4) the draw says so and returns a harmless number, the move commits nothing, and the caller rewinds the
-// stream and runs the same move out of line.
-template <bool kLeaf> EMAT_DF uint64_t rng_next64_t(Ctx& c) {
+EMAT_D uint64_t rng_next64(Ctx& c) {
   if (c.rng_has_spare) { c.rng_has_spare = false; return c.rng_spare; }
   if (k_rng_blocks != 0) {
     const uint64_t k = c.rng_ctr - c.rng_base;
@@ -384,10 +254,8 @@ template <bool kLeaf> EMAT_DF uint64_t rng_next64_t(Ctx& c) {
       return (uint64_t)w.x | ((uint64_t)w.y << 32);
     }
   }
-  if (kLeaf) { c.rng_short = true; return 0x8000000000000000ull; }
   return rng_next64_computed(c);
 }
-EMAT_D uint64_t rng_next64(Ctx& c) { return rng_next64_t<false>(c); }
 // All lanes: the blocks of the next k_rng_blocks counters (the caller synchronises the wave before and after).
 EMAT_D void rng_fill(Ctx& c, int lane) {
   if (k_rng_blocks == 0) return;
@@ -414,15 +282,6 @@ EMAT_D double u01_oc(Ctx& c) { return to_oc(rng_next64(c)); }
 EMAT_D double uniform_co(Ctx& c, double lo, double hi) { return lo + (hi - lo) * u01_co(c); }
 EMAT_D double uniform_oc(Ctx& c, double lo, double hi) { return lo + (hi - lo) * u01_oc(c); }
 EMAT_D int uniform_int(Ctx& c, int n) { return (int)__umul64hi(rng_next64(c), (uint64_t)n); }
-template <bool kLeaf> EMAT_DF double t_u01_co(Ctx& c) { return to_co(rng_next64_t<kLeaf>(c)); }
-template <bool kLeaf> EMAT_DF double t_u01_oo(Ctx& c) { return to_oo(rng_next64_t<kLeaf>(c)); }
-template <bool kLeaf> EMAT_DF double t_uniform_co(Ctx& c, double lo, double hi) { return lo + (hi - lo) * t_u01_co<kLeaf>(c); }
-template <bool kLeaf> EMAT_DF double t_uniform_oc(Ctx& c, double lo, double hi) { return lo + (hi - lo) * to_oc(rng_next64_t<kLeaf>(c)); }
-template <bool kLeaf> EMAT_DF int t_uniform_int(Ctx& c, int n) { return (int)__umul64hi(rng_next64_t<kLeaf>(c), (uint64_t)n); }
-// the four transcendentals: the shared out-of-line copy, or -- in a leaf move -- the same OCML routine inlined (the same numbers)
-template <bool kLeaf> EMAT_DF double t_log(double x) { if constexpr (kLeaf) return ::log(x); else return m_log(x); }
-template <bool kLeaf> EMAT_DF double t_exp(double x) { if constexpr (kLeaf) return ::exp(x); else return m_exp(x); }
-template <bool kLeaf> EMAT_DF double t_log1p(double x) { if constexpr (kLeaf) return ::log1p(x); else return m_log1p(x); }
 EMAT_D double gaussian(Ctx& c, double mean, double sigma) {
   uint64_t a = rng_next64(c), b = rng_next64(c);
   double u1 = to_oc(a), u2 = to_co(b);
@@ -496,7 +355,7 @@ template <class T> EMAT_DF bool sc_open_migrate(Ctx& c, SVec<T>& v, int max_elem
 template <class T> EMAT_DF void sc_trim(Ctx& c, SVec<T>& v, int line = __builtin_LINE()) {
   uint32_t used = ((uint32_t)v.n * (uint32_t)sizeof(T) + 15u) & ~15u;
   if (sc_in_lds(c, v.p)) { c.a_top = (uint32_t)((uint8_t*)v.p - c.A) + used; EMAT_COUNT(c, 9, used); EMAT_SITE(line, 0, used); }
-  else { c.sc_top = (uint32_t)((uint8_t*)v.p - c.G) + used; EMAT_COUNT(c, 8, used); EMAT_COUNT_TRIMS(c, 11, 1); EMAT_SITE(line, 1, used); }
+  else { c.sc_top = (uint32_t)((uint8_t*)v.p - c.G) + used; EMAT_COUNT(c, 8, used); EMAT_COUNT(c, 11, 1); EMAT_SITE(line, 1, used); }
   v.cap = v.n;
 }
 // Two containers growing towards each other inside one arena (results upwards from `lo`, a work stack downwards
@@ -532,7 +391,7 @@ EMAT_D ScSpan sc_span_hbm(Ctx& c) {
 EMAT_D void sc_span_commit(Ctx& c, const ScSpan& s, uint32_t used_bytes, int line = __builtin_LINE()) {
   uint32_t u = (used_bytes + 15u) & ~15u;
   if (s.reserved) return;   // the block stays reserved
-  if (s.lds) { c.a_top = (uint32_t)(s.lo - c.A) + u; EMAT_COUNT(c, 9, u); EMAT_SITE(line, 0, u); } else { c.sc_top = (uint32_t)(s.lo - c.G) + u; EMAT_COUNT(c, 8, u); EMAT_COUNT_TRIMS(c, 12, 1); EMAT_SITE(line, 1, u); }
+  if (s.lds) { c.a_top = (uint32_t)(s.lo - c.A) + u; EMAT_COUNT(c, 9, u); EMAT_SITE(line, 0, u); } else { c.sc_top = (uint32_t)(s.lo - c.G) + u; EMAT_COUNT(c, 8, u); EMAT_COUNT(c, 12, 1); EMAT_SITE(line, 1, u); }
 }
 
 // ---- persistent per-node lists in the slab heap ---------------------------------------------------------
@@ -902,16 +761,16 @@ EMAT_DF double skygrid_log_N_uniform(const EMAT_CONST_AS PopTable* p, double t) 
   const double cc = (t - x[k - 1]) / (x[k] - x[k - 1]);
   return (1 - cc) * ga[k - 1] + cc * ga[k];
 }
-template <bool kLeaf = false> EMAT_DF double log_pop_ratio_uniform(const PopTable* pp, double t_new, double t_old) {
+EMAT_DF double log_pop_ratio_uniform(const PopTable* pp, double t_new, double t_old) {
   const EMAT_CONST_AS PopTable* p = uniform_const_ptr(pp);
   const int kind = p->kind;
   if (kind == 0) return 0.0;
   t_new = uniform_f64(t_new); t_old = uniform_f64(t_old);
   if (kind == 2) return skygrid_log_N_uniform(p, t_new) - skygrid_log_N_uniform(p, t_old);
   const double t0 = p->p[0], n0 = p->p[1], gr = p->p[2], floor_n = p->p[3];
-  double a = n0 * t_exp<kLeaf>((t_new - t0) * gr); a = floor_n > a ? floor_n : a;
-  double b = n0 * t_exp<kLeaf>((t_old - t0) * gr); b = floor_n > b ? floor_n : b;
-  return t_log<kLeaf>(a / b);
+  double a = n0 * m_exp((t_new - t0) * gr); a = floor_n > a ? floor_n : a;
+  double b = n0 * m_exp((t_old - t0) * gr); b = floor_n > b ? floor_n : b;
+  return m_log(a / b);
 }
 EMAT_D double exp_unclamped_int(const PopTable& p, double a, double b) { double n0 = p.p[1], g = p.p[2], t0 = p.p[0]; return n0 / g * m_exp(g * (a - t0)) * m_expm1(g * (b - a)); }
 EMAT_DN double skygrid_log_int_N(const PopTable& p, double a, double b) {   // pop_model.cpp:247-330 with gamma_eff = gamma
@@ -1078,9 +937,9 @@ template <bool kGrow = true> EMAT_DF double coal_delta_on_add_interval(Ctx& c, d
   EMAT_COUNT(c, 13, cell_end - cell_start + 1); EMAT_COUNT(c, 14, 1);
   return d;
 }
-template <bool kGrow = true, bool kLeaf = false> EMAT_DF double coal_delta_displace_coalescence(Ctx& c, double old_t, double new_t) { EMAT_TIMED(0);   // cpp:310-326
+template <bool kGrow = true> EMAT_DF double coal_delta_displace_coalescence(Ctx& c, double old_t, double new_t) { EMAT_TIMED(0);   // cpp:310-326
   double d = (old_t <= new_t) ? coal_delta_on_add_interval<kGrow>(c, old_t, new_t, -1.0) : coal_delta_on_add_interval<kGrow>(c, new_t, old_t, +1.0);
-  { EMAT_TIMED(0); d -= log_pop_ratio_uniform<kLeaf>(c.pop, new_t, old_t); }
+  { EMAT_TIMED(0); d -= log_pop_ratio_uniform(c.pop, new_t, old_t); }
   return d;
 }
 template <bool kGrow = true> EMAT_DF double coal_delta_displace_tip(Ctx& c, double old_t, double new_t) {           // cpp:337-353

@@ -13,21 +13,20 @@ enum { k_inner_node_displace = 0, k_tip_displace = 1, k_branch_reform = 2, k_sub
 
 EMAT_D void begin_move(Ctx& c, int kind) { hdr_of(c)->proposed[kind]++; c.tr_kind = (double)kind; c.tr_node = -1.0; c.tr_acc = 0.0; c.tr_log_mh = __builtin_nan(""); }
 EMAT_D void note_move(Ctx& c, int node, double log_mh, bool acc, int kind) { c.tr_node = (double)node; c.tr_log_mh = log_mh; c.tr_acc = acc ? 1.0 : 0.0; if (acc) hdr_of(c)->accepted[kind]++; }
-template <bool kLeaf> EMAT_DF bool mh_accept_t(Ctx& c, double log_mh) { return log_mh >= 0.0 || t_uniform_co<kLeaf>(c, 0.0, 1.0) < t_exp<kLeaf>(log_mh); }
-EMAT_D bool mh_accept(Ctx& c, double log_mh) { return mh_accept_t<false>(c, log_mh); }
+EMAT_D bool mh_accept(Ctx& c, double log_mh) { return log_mh >= 0.0 || uniform_co(c, 0.0, 1.0) < m_exp(log_mh); }
 
 // distributions.h:38-69
-template <bool kLeaf = false> EMAT_DF double bounded_exponential(Ctx& c, double lambda, double a, double b) {
-  double u = t_u01_oo<kLeaf>(c);
+EMAT_DF double bounded_exponential(Ctx& c, double lambda, double a, double b) {
+  double u = u01_oo(c);
   double ltr = lambda * (b - a);
   double x;
   if (lambda == 0.0) x = a + u * (b - a);
-  else if (lambda > 0 && ltr > 100) x = b + t_log<kLeaf>(u) / lambda;
-  else if (lambda < 0 && ltr < -100) x = a + t_log<kLeaf>(u) / lambda;
-  else x = a + t_log1p<kLeaf>(u * (t_exp<kLeaf>(ltr) - 1)) / lambda;
+  else if (lambda > 0 && ltr > 100) x = b + m_log(u) / lambda;
+  else if (lambda < 0 && ltr < -100) x = a + m_log(u) / lambda;
+  else x = a + m_log1p(u * (m_exp(ltr) - 1)) / lambda;
   return x < a ? a : (b < x ? b : x);
 }
-template <bool kLeaf = false> EMAT_DF int pick_random_node(Ctx& c) { return t_uniform_int<kLeaf>(c, hdr_of(c)->n_nodes); }
+EMAT_DF int pick_random_node(Ctx& c) { return uniform_int(c, hdr_of(c)->n_nodes); }
 
 // subrun.cpp:683-742.  What the move keeps across its calls (the two grafts, the nodes and times it started from) lives in a
 // frame of the scratch arena, read back through the context after every call -- like an SPR1 move's Spr1Frame -- instead of
@@ -90,28 +89,14 @@ EMAT_NOTAIL EMAT_DN void spr_move_core(Ctx& c, int X, int new_branch, double new
 // displaced, its coalescent grid may grow, branch reforms next to the root go through spr_move_core) and kRoot = false for
 // every other part, where none of that can happen: those versions contain no root-only code, and their only calls are the
 // out-of-line transcendentals (m_log, m_exp, ...).
-// (-DEMAT_SIMPLE_MOVES_INLINE puts them inside run_chain_loop instead, which spares each simple move the whole-wave save
-// of the VGPR a non-leaf function parks its return address in -- scripts/micro/wwm.hip: ~490 cycles per call with one lane
-// active -- and costs 128 VGPRs and 544 B of scratch instead of 64 and 432: measured +0.3 %, not taken.)
-#ifndef EMAT_SIMPLE_MOVE
-#ifdef EMAT_SIMPLE_MOVES_INLINE
-#define EMAT_SIMPLE_MOVE EMAT_NOTAIL EMAT_DF
-#else
-#define EMAT_SIMPLE_MOVE EMAT_NOTAIL EMAT_DN
-#endif
-#endif
-// kLeaf (only with kRoot = false): the move as a LEAF function -- transcendentals inlined, draws that cannot call -- which returns true when it ran out of
-// numbers computed ahead and must be run again out of line (mcmc_sub_iteration); nothing is committed in that case (the check sits between the last draw,
-// mh_accept's, and the first store to the part's state).
-template <bool kRoot, bool kLeaf = false> EMAT_SIMPLE_MOVE bool inner_node_displace_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:148-232
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void inner_node_displace_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:148-232
   begin_move(c, k_inner_node_displace);
   int node;
   { EMAT_TIMED(2);   /* inner_displace: pick an inner node */
-    int guard = 0; do { node = pick_random_node<kLeaf>(c); } while (is_tip(c, node) && !(kLeaf && c.rng_short) && guard++ < (1 << 26)); }
-  if (kLeaf && c.rng_short) return true;
+    int guard = 0; do { node = pick_random_node(c); } while (is_tip(c, node) && guard++ < (1 << 26)); }
   c.tr_node = (double)node;
   const int root = hdr_of(c)->root;
-  if (!kRoot && node == root) return kLeaf && c.rng_short;   // node == root && !includes_run_root
+  if (!kRoot && node == root) return;   // node == root && !includes_run_root
   const NodeRec nd = nodes_of(c)[node];
   double t_min = -k_inf;
   if (!kRoot || node != root) {
@@ -147,23 +132,22 @@ template <bool kRoot, bool kLeaf = false> EMAT_SIMPLE_MOVE bool inner_node_displ
     double delta_scale;   // std::min(ds, tree_span)
     if (tree_span < ds) delta_scale = tree_span; else delta_scale = ds;
     new_t = old_t + gaussian(c, 0.0, delta_scale);
-    if (new_t < t_min || new_t > t_max) return false;
+    if (new_t < t_min || new_t > t_max) return;
     log_alpha_ratio = 0.0;
   } else {
     EMAT_TIMED(2);   /* inner_displace: bounded_exponential */
-    new_t = bounded_exponential<kLeaf>(c, d_logG_dt, t_min, t_max);
+    new_t = bounded_exponential(c, d_logG_dt, t_min, t_max);
     log_alpha_ratio = d_logG_dt * (new_t - old_t);
   }
-  if (new_t == t_min || new_t == t_max) return kLeaf && c.rng_short;
-  if (kRoot) { if (coal_needs_cells(c, new_t)) { stop_for_cells(c, k_inner_node_displace); return false; } }   // nothing has changed yet
+  if (new_t == t_min || new_t == t_max) return;
+  if (kRoot) { if (coal_needs_cells(c, new_t)) { stop_for_cells(c, k_inner_node_displace); return; } }   // nothing has changed yet
   double delta_log_G = d_logG_dt * (new_t - old_t);
-  double delta_log_prior = coal_delta_displace_coalescence<kRoot, kLeaf>(c, old_t, new_t);
-  if (c.failed) return kLeaf && c.rng_short;
+  double delta_log_prior = coal_delta_displace_coalescence<kRoot>(c, old_t, new_t);
+  if (c.failed) return;
   double log_mh = delta_log_G + delta_log_prior - log_alpha_ratio;
   bool acc;
   { EMAT_TIMED(2);   /* inner_displace: mh_accept + note_move */
-  acc = mh_accept_t<kLeaf>(c, log_mh);
-  if (kLeaf && c.rng_short) return true;   // (the last draw: nothing of the part has been written yet)
+  acc = mh_accept(c, log_mh);
   note_move(c, node, log_mh, acc, k_inner_node_displace); }
   if (acc) {
     EMAT_TIMED(2);   /* inner_displace: accepted: coal_coalescence_displaced + updates */
@@ -172,17 +156,15 @@ template <bool kRoot, bool kLeaf = false> EMAT_SIMPLE_MOVE bool inner_node_displ
     hdr_of(c)->log_G += d_logG_dt * (new_t - old_t);
     hdr_of(c)->log_aug_prior += delta_log_prior;
   }
-  return false;
 }
 
-template <bool kRoot, bool kLeaf = false> EMAT_SIMPLE_MOVE bool tip_displace_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:234-285
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void tip_displace_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:234-285
   begin_move(c, k_tip_displace);
   int node;
-  { int guard = 0; do { node = pick_random_node<kLeaf>(c); } while (!is_tip(c, node) && !(kLeaf && c.rng_short) && guard++ < (1 << 26)); }
-  if (kLeaf && c.rng_short) return true;
+  { int guard = 0; do { node = pick_random_node(c); } while (!is_tip(c, node) && guard++ < (1 << 26)); }
   c.tr_node = (double)node;
   const NodeRec nd = nodes_of(c)[node];
-  if (nd.t_min == nd.t_max) return kLeaf && c.rng_short;
+  if (nd.t_min == nd.t_max) return;
   double t_min;   // std::max(a, b) = a < b ? b : a
   if ((double)nd.t_min < nodes_of(c)[nd.parent].t) t_min = nodes_of(c)[nd.parent].t; else t_min = (double)nd.t_min;
   const MutRec* m = muts_of(c, node);
@@ -191,15 +173,14 @@ template <bool kRoot, bool kLeaf = false> EMAT_SIMPLE_MOVE bool tip_displace_mov
   const double d_logG_dt = -nd.lambda;
   const double old_t = nd.t;
   c.bytes += 2 * 64 + 16 * (int)nd.muts.cnt;
-  double new_t = bounded_exponential<kLeaf>(c, d_logG_dt, t_min, t_max);
+  double new_t = bounded_exponential(c, d_logG_dt, t_min, t_max);
   double log_alpha_ratio = d_logG_dt * (new_t - old_t);
-  if (new_t == t_min || new_t == t_max) return kLeaf && c.rng_short;
+  if (new_t == t_min || new_t == t_max) return;
   double delta_log_G = d_logG_dt * (new_t - old_t);
   double delta_log_prior = coal_delta_displace_tip<kRoot>(c, old_t, new_t);
-  if (c.failed) return kLeaf && c.rng_short;
+  if (c.failed) return;
   double log_mh = delta_log_G + delta_log_prior - log_alpha_ratio;
-  bool acc = mh_accept_t<kLeaf>(c, log_mh);
-  if (kLeaf && c.rng_short) return true;   // (the last draw: nothing of the part has been written yet)
+  bool acc = mh_accept(c, log_mh);
   note_move(c, node, log_mh, acc, k_tip_displace);
   if (acc) {
     coal_tip_displaced<kRoot>(c, old_t, new_t);
@@ -207,11 +188,10 @@ template <bool kRoot, bool kLeaf = false> EMAT_SIMPLE_MOVE bool tip_displace_mov
     hdr_of(c)->log_G += d_logG_dt * (new_t - old_t);
     hdr_of(c)->log_aug_prior += delta_log_prior;
   }
-  return false;
 }
 
 // phylo_tree.cpp:579-644; result in scratch
-template <bool kLeaf = false> EMAT_DF SVec<MutRec> randomize_branch_mutation_times(Ctx& c, int X) { EMAT_TIMED(2);
+EMAT_DF SVec<MutRec> randomize_branch_mutation_times(Ctx& c, int X) { EMAT_TIMED(2);
   const int n = nmuts(c, X);
   SVec<MutRec> out = sc_vec<MutRec>(c, n);
   if (c.failed) return out;
@@ -221,7 +201,7 @@ template <bool kLeaf = false> EMAT_DF SVec<MutRec> randomize_branch_mutation_tim
   bool complicated = false;
   for (int i = 0; i < n && !complicated; ++i) for (int j = i + 1; j < n; ++j) if (old[i].site == old[j].site) { complicated = true; break; }
   if (!complicated) {
-    for (int i = 0; i < n; ++i) { MutRec r = make_mut(old[i].from, old[i].site, old[i].to, t_uniform_oc<kLeaf>(c, t_P, t_X)); r.pad = (uint16_t)i; push(c, out, r); }   // pad: where it came from (reform_factors)
+    for (int i = 0; i < n; ++i) { MutRec r = make_mut(old[i].from, old[i].site, old[i].to, uniform_oc(c, t_P, t_X)); r.pad = (uint16_t)i; push(c, out, r); }   // pad: where it came from (reform_factors)
   } else {
     // distinct sites in ascending order; per site, fresh sorted times assigned in the old order
     int prev_site = -1;
@@ -231,7 +211,7 @@ template <bool kLeaf = false> EMAT_DF SVec<MutRec> randomize_branch_mutation_tim
       if (l == 0x7fffffff) break;
       prev_site = l;
       int first = out.n, k = 0;
-      for (int i = 0; i < n; ++i) if (old[i].site == l) { MutRec r = make_mut(old[i].from, old[i].site, old[i].to, t_uniform_oc<kLeaf>(c, t_P, t_X)); r.pad = (uint16_t)i; push(c, out, r); ++k; }
+      for (int i = 0; i < n; ++i) if (old[i].site == l) { MutRec r = make_mut(old[i].from, old[i].site, old[i].to, uniform_oc(c, t_P, t_X)); r.pad = (uint16_t)i; push(c, out, r); ++k; }
       // sort just the times of this site's block
       for (int a = first + 1; a < first + k && a < out.n; ++a) { double x = out.p[a].t; int b = a - 1; while (b >= first && out.p[b].t > x) { out.p[b + 1].t = out.p[b].t; --b; } out.p[b + 1].t = x; }
     }
@@ -247,7 +227,7 @@ template <bool kLeaf = false> EMAT_DF SVec<MutRec> randomize_branch_mutation_tim
 // and one logarithm per mutation and list, in sequence), and each sum then runs in its own order over the same operands -- bit
 // for bit the reference's two numbers.  A re-timed mutation carries the index of the one it came from in its `pad` field.
 struct ReformFactors { double* A; double* B; };
-template <bool kLeaf = false> EMAT_DF ReformFactors reform_factors(Ctx& c, const MutRec* m, int n) { EMAT_TIMED(2);
+EMAT_DF ReformFactors reform_factors(Ctx& c, const MutRec* m, int n) { EMAT_TIMED(2);
   ReformFactors f; f.A = (double*)sc_alloc(c, (uint32_t)n * 16u); f.B = f.A + n;
   if (c.failed) return f;
   uint32_t need_log = 0u; bool all_logs = false;   // which entries still hold the logarithm's argument (bit j for j < 32; beyond: decided again per entry)
@@ -267,22 +247,21 @@ template <bool kLeaf = false> EMAT_DF ReformFactors reform_factors(Ctx& c, const
       else { f.B[j0 + k] = mn * q[(int)mm.from * 4 + (int)mm.to]; need_log |= 1u << ((j0 + k) & 31); if (j0 + k >= 32) all_logs = true; }   // the logarithm's argument; taken below
     }
   }
-  if (all_logs) { for (int j = 0; j < n; ++j) if (!(c.have_logq && site_nu(c, m[j].site) == 1.0)) f.B[j] = t_log<kLeaf>(f.B[j]); }
-  else if (need_log != 0u) { const int n32 = n < 32 ? n : 32; for (int j = 0; j < n32; ++j) if ((need_log >> j) & 1u) f.B[j] = t_log<kLeaf>(f.B[j]); }   // entries from 32 on need none (all_logs would be set): never shift by >= 32
+  if (all_logs) { for (int j = 0; j < n; ++j) if (!(c.have_logq && site_nu(c, m[j].site) == 1.0)) f.B[j] = m_log(f.B[j]); }
+  else if (need_log != 0u) { const int n32 = n < 32 ? n : 32; for (int j = 0; j < n32; ++j) if ((need_log >> j) & 1u) f.B[j] = m_log(f.B[j]); }   // entries from 32 on need none (all_logs would be set): never shift by >= 32
   return f;
 }
-template <bool kRoot, bool kLeaf = false> EMAT_SIMPLE_MOVE bool branch_reform_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:287-320
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void branch_reform_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:287-320
   begin_move(c, k_branch_reform);
-  if (hdr_of(c)->n_nodes < 3) return false;
-  const int X = pick_random_node<kLeaf>(c);
+  if (hdr_of(c)->n_nodes < 3) return;
+  const int X = pick_random_node(c);
   c.tr_node = (double)X;
-  if (kLeaf && c.rng_short) return true;
-  if (X == hdr_of(c)->root) return false;
+  if (X == hdr_of(c)->root) return;
   const int P = nodes_of(c)[X].parent;
   const int S = sibling_of(c, P, X);
   const double t_X = nodes_of(c)[X].t, t_P = nodes_of(c)[P].t;
   // in a part without the run's root, spr_move_core returns at once for a branch next to the subroot (subrun.cpp:689-697)
-  if (kRoot) { if (P == hdr_of(c)->root) { spr_move_core(c, X, S, t_P, 1.0); if (c.failed) return false; } }
+  if (kRoot) { if (P == hdr_of(c)->root) { spr_move_core(c, X, S, t_P, 1.0); if (c.failed) return; } }
   const double lam = nodes_of(c)[X].lambda;
   const int n = nmuts(c, X);
   if (n == 0) {
@@ -290,35 +269,26 @@ template <bool kRoot, bool kLeaf = false> EMAT_SIMPLE_MOVE bool branch_reform_mo
     // number is drawn, and the empty list replaces itself
     const double g = -lam * (t_X - t_P), delta_log_G = g - g;
     c.bytes += 2 * 64;
-    const bool acc = mh_accept_t<kLeaf>(c, delta_log_G);
-    if (kLeaf && c.rng_short) return true;
+    const bool acc = mh_accept(c, delta_log_G);
     note_move(c, X, delta_log_G, acc, k_branch_reform);
     if (acc) hdr_of(c)->log_G += delta_log_G;
-    return false;
+    return;
   }
-#ifdef EMAT_X_NO_FACTORS
-  SVec<MutRec> nm = randomize_branch_mutation_times<kLeaf>(c, X);
-  if (c.failed) return kLeaf && c.rng_short;
-  const double delta_log_G = branch_log_G(c, t_P, t_X, lam, nm.p, nm.n) - branch_log_G(c, t_P, t_X, lam, muts_of(c, X), nmuts(c, X));
-#else
-  const ReformFactors f = reform_factors<kLeaf>(c, muts_of(c, X), n);
-  SVec<MutRec> nm = randomize_branch_mutation_times<kLeaf>(c, X);
-  if (c.failed) return kLeaf && c.rng_short;
+  const ReformFactors f = reform_factors(c, muts_of(c, X), n);
+  SVec<MutRec> nm = randomize_branch_mutation_times(c, X);
+  if (c.failed) return;
   double g_new = -lam * (t_X - t_P), g_old = g_new;
   { const MutRec* m = nm.p; for (int i = nm.n - 1; i >= 0; --i) { const int j = (int)m[i].pad; g_new -= f.A[j] * (m[i].t - t_P); g_new += f.B[j]; } }
   { const MutRec* m = muts_of(c, X); for (int i = n - 1; i >= 0; --i) { g_old -= f.A[i] * (m[i].t - t_P); g_old += f.B[i]; } }
   const double delta_log_G = g_new - g_old;
-#endif
   c.bytes += 2 * 64 + 2 * 16 * nm.n;
   double log_mh = delta_log_G;
-  bool acc = mh_accept_t<kLeaf>(c, log_mh);
-  if (kLeaf && c.rng_short) return true;   // (the last draw: nothing of the part has been written yet)
+  bool acc = mh_accept(c, log_mh);
   note_move(c, X, log_mh, acc, k_branch_reform);
   if (acc) {
     for (int i = 0; i < nm.n; ++i) nm.p[i].pad = 0;
     list_assign<MutRec>(c, nodes_of(c)[X].muts, nm.p, nm.n); hdr_of(c)->log_G += delta_log_G; c.bytes += 16 * nm.n; c.bytes_w += 16 * nm.n;
   }
-  return false;
 }
 
 // subrun.cpp:325-350, iterative with an explicit stack in scratch
@@ -404,11 +374,7 @@ EMAT_NOTAIL EMAT_DN void spr1_move_begin(Ctx& c) { EMAT_TIMED(2);
   c.phase = 0;
   if (hdr_of(c)->n_nodes < 2) return;
   const double chooser = uniform_co(c, 0.0, 1.0);
-#ifdef EMAT_X_NO_UNLIMITED_SCANS   // timing experiment only (a different chain): what the 1 % of scans without a limit cost the slowest chains
-  const int limit = 1; (void)chooser;
-#else
   const int limit = chooser < 0.01 ? 0x7fffffff : 1;
-#endif
   const int root0 = hdr_of(c)->root;
   c.mu_prop = nodes_of(c)[root0].lambda / (c.L - nodes_of(c)[root0].n_missing);
   int X;
@@ -578,32 +544,22 @@ EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
   sc_reset(c);
   c.mv_rng_ctr = c.rng_ctr; c.mv_rng_had_spare = c.rng_has_spare;
   c.tr_kind = -1.0; c.tr_node = -1.0; c.tr_acc = 0.0; c.tr_log_mh = __builtin_nan("");
-  // -DEMAT_LEAF_SIMPLE=1: a part without the run's root runs its simple moves as LEAF functions (transcendentals inlined, draws that cannot call: no return address
-  // to park, no whole-wave save and reload around every move); one that ran out of numbers computed ahead has committed nothing: its counters are put back, the
-  // stream is rewound to the move's first draw, and the same move runs out of line.  Built and measured in round 6 -- the leaf versions contain no call and no
-  // scratch access, all trajectory-parity tests pass on them -- and worth NOTHING: 476.4 against 476.7 M moves/s, HBM writes unchanged: off.
-#ifndef EMAT_LEAF_SIMPLE
-#define EMAT_LEAF_SIMPLE 0
-#endif
-  const bool leaf = EMAT_LEAF_SIMPLE && !c.includes_run_root;
-  const int64_t bytes0 = c.bytes, bytes_w0 = c.bytes_w;
-  auto redo = [&](int kind) { hdr_of(c)->proposed[kind]--; c.bytes = bytes0; c.bytes_w = bytes_w0; c.rng_short = false; rng_rewind_to_move_start(c); };
   if (c.only_displacing_inner_nodes) {
     if (c.includes_run_root) inner_node_displace_move<true>(c);
-    else if (!leaf || inner_node_displace_move<false, true>(c)) { if (leaf) redo(k_inner_node_displace); inner_node_displace_move<false>(c); }
+    else inner_node_displace_move<false>(c);
   } else {
     double total_weight = 15.0 + 15.0;
     if (c.topology_moves_enabled) total_weight += 1.0 + 1.0;
     double r = uniform_co(c, 0.0, total_weight);
     if (r < 7.5) {
       if (c.includes_run_root) inner_node_displace_move<true>(c);
-      else if (!leaf || inner_node_displace_move<false, true>(c)) { if (leaf) { redo(k_inner_node_displace); (void)uniform_co(c, 0.0, total_weight); } inner_node_displace_move<false>(c); }
+      else inner_node_displace_move<false>(c);
     } else if (r < 15.0) {
       if (c.includes_run_root) tip_displace_move<true>(c);
-      else if (!leaf || tip_displace_move<false, true>(c)) { if (leaf) { redo(k_tip_displace); (void)uniform_co(c, 0.0, total_weight); } tip_displace_move<false>(c); }
+      else tip_displace_move<false>(c);
     } else if (r < 30.0) {
       if (c.includes_run_root) branch_reform_move<true>(c);
-      else if (!leaf || branch_reform_move<false, true>(c)) { if (leaf) { redo(k_branch_reform); (void)uniform_co(c, 0.0, total_weight); } branch_reform_move<false>(c); }
+      else branch_reform_move<false>(c);
     }
     else if (c.topology_moves_enabled) { if (r < 31.0) subtree_slide_move(c); else spr1_move_begin(c); }
   }

@@ -132,7 +132,7 @@ EMAT_DN Edit edit_slide_root_v(Ctx& c, Edit e, double new_t_P) {   // tree_editi
   return e;
 }
 EMAT_DF void edit_slide_root(Ctx& c, Edit& e, double new_t_P) { e = edit_slide_root_v(c, e, new_t_P); }
-EMAT_FN_SLIDE Edit edit_slide_P_along_branch_v(Ctx& c, Edit e, double new_t_P) {   // tree_editing.cpp:31-112
+EMAT_DF Edit edit_slide_P_along_branch_v(Ctx& c, Edit e, double new_t_P) {   // tree_editing.cpp:31-112
   const int X = e.X, P = nodes_of(c)[X].parent;
   EMAT_CHECK(c, !is_tip(c, P));
   if (P == hdr_of(c)->root) return edit_slide_root_v(c, e, new_t_P);
@@ -185,7 +185,7 @@ EMAT_FN_SLIDE Edit edit_slide_P_along_branch_v(Ctx& c, Edit e, double new_t_P) {
   return e;
 }
 EMAT_DF void edit_slide_P_along_branch(Ctx& c, Edit& e, double new_t_P) { e = edit_slide_P_along_branch_v(c, e, new_t_P); }
-EMAT_FN_HOP void edit_do_hop_up(Ctx& c, int X) {   // tree_editing.cpp:164-231
+EMAT_DF void edit_do_hop_up(Ctx& c, int X) {   // tree_editing.cpp:164-231
   EMAT_CHECK(c, X != hdr_of(c)->root);
   const int P = nodes_of(c)[X].parent;
   EMAT_CHECK(c, !is_tip(c, P) && P != hdr_of(c)->root && nmuts(c, P) == 0);
@@ -274,7 +274,7 @@ EMAT_DF void edit_end(Ctx& c, Edit& e) {
   }
 }
 // spr_move.cpp:1101-1156
-EMAT_FN_TOPO void spr_move_topology(Ctx& c, int X, int SS, double new_t_P) { EMAT_TIMED(1);
+EMAT_DN void spr_move_topology(Ctx& c, int X, int SS, double new_t_P) { EMAT_TIMED(1);
   if (c.failed) return;
   EMAT_CHECK(c, X != hdr_of(c)->root);
   const int P = nodes_of(c)[X].parent, G = nodes_of(c)[P].parent, S = sibling_of(c, P, X);
@@ -339,7 +339,7 @@ EMAT_DF KTruncPoisson ktp_make(double lambda, int min_k) {   // (inlined into it
 // (the distribution's five numbers as scalar arguments: a struct of 40 bytes passed by value goes through the caller's private frame all the same)
 // (Inlined into the trajectory sampler, and that into the history sampler, since round 6: three rejection rounds per constrained site, each a call of this and
 // each call a whole-wave save and its reload -- out of line they cost 1.2 % of a pass)
-EMAT_FN_KTP int ktp_sample_s(Ctx& c, double lambda, int min_k, double normalization, double term_before_min_k, double max_k) {
+EMAT_DF int ktp_sample_s(Ctx& c, double lambda, int min_k, double normalization, double term_before_min_k, double max_k) {
   KTruncPoisson d; d.lambda = lambda; d.min_k = min_k; d.normalization = normalization; d.term_before_min_k = term_before_min_k; d.max_k = max_k;
   if (d.normalization == 0.0) { int guard = 0; while (guard++ < (1 << 26)) { int k = poisson(c, d.lambda); if (k >= d.min_k) return k; } return d.min_k; }
   double u = uniform_co(c, 0.0, d.normalization);
@@ -360,7 +360,7 @@ EMAT_DF bool open_room(Ctx& c, SVec<MutRec>& out, int extra) {
 }
 // (The vector's header by value, in and out, and the distribution as scalars: see sd_push_front_v.  The trajectory was accepted exactly when the
 // vector came back longer: a trajectory has at least min_k >= 1 mutations.)
-EMAT_FN_SST SVec<MutRec> sample_site_trajectory_v(Ctx& c, SVec<MutRec> out, int l, int from, int to, double d_lambda, int d_min_k, double d_normalization, double d_term_before_min_k, double d_max_k,
+EMAT_DF SVec<MutRec> sample_site_trajectory_v(Ctx& c, SVec<MutRec> out, int l, int from, int to, double d_lambda, int d_min_k, double d_normalization, double d_term_before_min_k, double d_max_k,
                                               double T, bool accept_only_if_match) {
   int n = 0; int s = from;
   int guard = 0;
@@ -389,23 +389,18 @@ EMAT_DF void sample_site_trajectory(Ctx& c, SVec<MutRec>& out, int l, int from, 
   out = r;
 }
 // spr_move.cpp:1164-1370; result appended into a fresh open-ended scratch vector (caller trims)
-EMAT_FN_SMH SVec<MutRec> sample_mutational_history(Ctx& c, int L, double T, double mu, const SVec<SdRec>& deltas) { EMAT_TIMED(1);
+EMAT_DF SVec<MutRec> sample_mutational_history(Ctx& c, int L, double T, double mu, const SVec<SdRec>& deltas) { EMAT_TIMED(1);
   // the LDS arena if it has room for the constrained sites (one mutation each, rarely three) and the L (mu T)^2 / 2 other sites
   // expected to be hit twice or more on a long branch; should more turn up, the vector moves to HBM (open_room)
   const double twice = 0.5 * (double)L * (mu * T) * (mu * T);
   const int want = 2 * deltas.n + 8 + (twice < 1e6 ? (int)(3.0 * twice + 6.0 * sqrt(3.0 * twice)) : (1 << 20));
   SVec<MutRec> out = sc_open<MutRec>(c, k_open_max, want);
   if (c.failed) return out;
-#ifdef EMAT_X_TRIVIAL_CONSTRAINED   // timing experiment only (a different chain, parity gone): every constrained site gets ONE mutation at the branch's midpoint without a draw --
-  // what the pass would take if the per-site rejection sampling cost nothing: the bound on what per-site streams spread over the wavefront could buy
-  if (deltas.n != 0 && open_room(c, out, deltas.n)) { for (int i = 0; i < deltas.n; ++i) out.p[out.n++] = make_mut(deltas.p[i].from, deltas.p[i].site, deltas.p[i].to, -0.5 * T); }
-#else
   if (deltas.n != 0) { EMAT_TIMED(1);   /* sample_history: constrained sites (ktp_make + one trajectory per delta) */
     KTruncPoisson ge1 = ktp_make(mu * T, 1);
     for (int i = 0; i < deltas.n && !c.failed; ++i) { EMAT_TIMED(1);   /* sample_history: ONE constrained site */
       bool acc; sample_site_trajectory(c, out, deltas.p[i].site, deltas.p[i].from, deltas.p[i].to, ge1, T, true, acc); }
   }
-#endif
   double muT = mu * T;
   int l = 0;
   if ((double)L * muT * muT < 2e-6) l = L;
@@ -455,7 +450,7 @@ EMAT_DN SVec<MutRec> sample_unconstrained_mutational_history(Ctx& c, int L, doub
   return out;
 }
 // spr_move.cpp:1409-1439
-EMAT_FN_ADJ void adjust_mutational_history(Ctx& c, const SVec<MutRec> h, const SVec<SdRec> deltas, int end_branch, double end_t) { EMAT_TIMED(1);   // (headers by value: only the records change)
+EMAT_DF void adjust_mutational_history(Ctx& c, const SVec<MutRec> h, const SVec<SdRec> deltas, int end_branch, double end_t) { EMAT_TIMED(1);   // (headers by value: only the records change)
   for (int i = h.n - 1; i >= 0; --i) {
     MutRec& m = h.p[i];
     m.t += end_t;
@@ -651,7 +646,7 @@ EMAT_DN void apply_rooty_graft(Ctx& c, const Graft& g) { EMAT_TIMED(1);   // spr
 }
 
 // ---- inner grafts -----------------------------------------------------------------------------------------
-EMAT_FN_START void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:582-738
+EMAT_DN void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:582-738
   g.X = X; g.rooty = false; g.delta_log_G = g.log_alpha_mut = 0.0; g.nbi = 0; g.bi = nullptr;
   const int P = nodes_of(c)[X].parent;
   EMAT_CHECK(c, X != hdr_of(c)->root && P != hdr_of(c)->root);
@@ -769,7 +764,7 @@ EMAT_FN_START void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TI
   } }
   return;
 }
-EMAT_FN_PNIG void propose_new_inner_graft_mutations(Ctx& c, Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:740-785
+EMAT_DF void propose_new_inner_graft_mutations(Ctx& c, Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:740-785
   const int X = g.X;
   for (int idx = 0; idx < g.nbi && !c.failed; ++idx) {
     BranchInfo& bi = g.bi[idx];
@@ -791,7 +786,7 @@ EMAT_FN_PNIG void propose_new_inner_graft_mutations(Ctx& c, Graft& g) { EMAT_TIM
     recompute_open_pl_A(c, bi);
   }
 }
-EMAT_FN_FINI void finish_inner_graft_analysis(Ctx& c, Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:787-836
+EMAT_DF void finish_inner_graft_analysis(Ctx& c, Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:787-836
   if (c.failed || g.nbi == 0) return;
   const int X = g.X; const double t_X = nodes_of(c)[X].t;
   g.delta_log_G = 0.0;
@@ -810,7 +805,7 @@ EMAT_D void recalc_lambda_along_hot_path(Ctx& c, const Graft& g) {   // spr_move
   for (int i = 0; i + 1 < g.nbi; ++i) { int A = g.bi[i].A, B = g.bi[i].B; nodes_of(c)[A].lambda = nodes_of(c)[B].lambda - delta_lambda_across_branch(c, B); }
 }
 EMAT_D void erase_marked_muts(Ctx& c, int node) { MutRec* m = muts_of(c, node); int n = nmuts(c, node), w = 0; for (int i = 0; i < n; ++i) if (m[i].site != -1) m[w++] = m[i]; set_list_cnt(c, nodes_of(c)[node].muts, w); }
-EMAT_FN_PEEL void peel_inner_graft(Ctx& c, const Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:838-953
+EMAT_DF void peel_inner_graft(Ctx& c, const Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:838-953
   if (c.failed || g.nbi == 0) return;
   const int X = g.X, P = nodes_of(c)[X].parent, root = hdr_of(c)->root;
   const double t_X = nodes_of(c)[X].t, t_P = nodes_of(c)[P].t;
@@ -859,7 +854,7 @@ EMAT_FN_PEEL void peel_inner_graft(Ctx& c, const Graft& g) { EMAT_TIMED(1);   //
   recalc_lambda_along_hot_path(c, g);
   sc_release(c, mark);
 }
-EMAT_FN_APPLY void apply_inner_graft(Ctx& c, const Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:955-1069
+EMAT_DF void apply_inner_graft(Ctx& c, const Graft& g) { EMAT_TIMED(1);   // spr_move.cpp:955-1069
   if (c.failed || g.nbi == 0) return;
   const int X = g.X, root = hdr_of(c)->root;
   const BranchInfo& fin = g.bi[g.nbi - 1];
@@ -918,7 +913,7 @@ EMAT_D int count_min_mutations(const Ctx& c, const Graft& g) {
   int r = 0; for (int i = 0; i < g.nbi; ++i) if (!g.bi[i].is_open) r += g.bi[i].hot_deltas.n; return r;
 }
 // summarize_closed_mutations: fresh scratch delta list with room for `extra` more entries
-EMAT_FN_SUMM SVec<SdRec> summarize_closed_mutations(Ctx& c, const Graft& g, int extra) { EMAT_TIMED(1);
+EMAT_DF SVec<SdRec> summarize_closed_mutations(Ctx& c, const Graft& g, int extra) { EMAT_TIMED(1);
   int tot = 0;
   if (g.rooty) tot = g.bi[k_SPX].hot_deltas.n; else for (int i = 0; i < g.nbi; ++i) if (!g.bi[i].is_open) tot += g.bi[i].hot_deltas.n;
   SVec<SdRec> r = sc_vec<SdRec>(c, tot + extra + 1);
@@ -1221,7 +1216,7 @@ EMAT_D int study_pick_nexus_region(Ctx& c, const Study& st) {   // spr_study.cpp
   for (int i = 0; i < st.regions.n; ++i) { if (st.regions.p[i].W >= r) return i; r -= st.regions.p[i].W; }
   return 0;
 }
-EMAT_FN_PICKT double study_pick_time_in_region(Ctx& c, const Study& st, int idx) {   // spr_study.cpp:424-471
+EMAT_DF double study_pick_time_in_region(Ctx& c, const Study& st, int idx) {   // spr_study.cpp:424-471
   const Region& r = st.regions.p[idx];
   if (r.t_min != k_neg_dbl_max) return uniform_oc(c, r.t_min, r.t_max);
   RootRegionParams p = root_region_params(c, st, r);
@@ -1249,7 +1244,7 @@ EMAT_D int study_find_region(const Study& st, int branch, double t) {   // spr_s
   for (int i = 0; i < st.regions.n; ++i) { const Region& r = st.regions.p[i]; if (r.branch == branch && r.t_min < t && t <= r.t_max) return i; }
   return -1;
 }
-EMAT_FN_LALPHA double study_log_alpha_in_region(Ctx& c, const Study& st, int idx, double t) {   // spr_study.cpp:486-549
+EMAT_DF double study_log_alpha_in_region(Ctx& c, const Study& st, int idx, double t) {   // spr_study.cpp:486-549
   const Region& r = st.regions.p[idx];
   double log_p_region = r.logW - m_log(st.sum_W);
   if (r.t_min != k_neg_dbl_max) return log_p_region - m_log(r.t_max - r.t_min);
@@ -1561,14 +1556,8 @@ EMAT_DN void wave_scan_and_study(Ctx& c) {
   if (fr.limit == 1) scanned = wave_local_scan(c, fr);
 #endif
   if (!scanned) {   // the 1 % of scans without a limit on the mutations crossed (and local ones that found no room): serial, on lane 0
-#if defined(EMAT_PROFILE_PHASES) && defined(EMAT_X_UNLIMITED_SCANS)
-    const long long un0 = clock64();
-#endif
     if (lane == 0) *shared = study_seed_fill(c, fr.X, fr.t_X, fr.missing_at_X, fr.limit, fr.init_branch, 0, fr.deltas, fr.can_change_root, fr.hot);
     __syncthreads();
-#if defined(EMAT_PROFILE_PHASES) && defined(EMAT_X_UNLIMITED_SCANS)
-    if (lane == 0) { EMAT_COUNT(c, 11, 1); EMAT_COUNT(c, 12, clock64() - un0); }
-#endif
   }
 #ifdef EMAT_PROFILE_PHASES
   if (lane == 0) { hdr_of(c)->phase_ticks[6] += clock64() - ph0; hdr_of(c)->phase_ticks[13] += shared->n; }
