@@ -852,7 +852,7 @@ __global__ void __launch_bounds__(k_wave) EMAT_OCCUPANCY k_debug_gamma(const dou
 // ---- test hooks: the device's population-model and interval-set routines on plain inputs (emat_debug_pop, _interval_op) --
 __global__ void __launch_bounds__(k_wave) EMAT_OCCUPANCY k_debug_pop(PopTable pt, int op, const double* a, const double* b, double* out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = op == 0 ? dev::pop_at_time(pt, a[i]) : dev::pop_integral(pt, a[i], b[i]);
+  if (i < n) out[i] = op == 0 ? dev::pop_at_time(pt, a[i]) : op == 1 ? dev::pop_integral(pt, a[i], b[i]) : dev::pop_intensity_integral(pt, a[i], b[i]);
 }
 __global__ void k_debug_interval_op(int op, const IvRec* A, int nA, const IvRec* B, int nB, int site, IvRec* out, int* n_out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -867,6 +867,7 @@ __global__ void k_debug_interval_op(int op, const IvRec* A, int nA, const IvRec*
 }  // namespace emat
 #include "emat_gtree_kernels.hpp"   // the whole tree in HBM: cutting it into part slabs and gathering the parts back
 #include "emat_build.hpp"           // initial-tree construction: the graft loop as a kernel, the finishing passes on the host
+#include "emat_probe_kernels.hpp"   // the tree probers on the resident tree: lineage and site-state prevalence over time
 namespace emat {
 
 // =================================================================================================
@@ -989,6 +990,13 @@ struct GTreeHost {
   GPools pools() { GPools q{}; q.muts = pool_muts.p; q.ivs = pool_ivs.p; q.mut_cap = (uint32_t)pool_muts.n; q.iv_cap = (uint32_t)pool_ivs.n; q.tops = pool_tops.p; return q; }
 };
 
+// Scratch of the tree probers (emat_probe_kernels.hpp, emat_probe_host.hpp): allocated at the first call, grown on demand.
+struct ProbeScratch {
+  DevBuf<int32_t> val, jump_a, jump_b, marked, diff, status;
+  DevBuf<unsigned long long> fix;
+  DevBuf<double> counts, total, p_coalesce, p, sky_x, sky_g;
+};
+
 }  // namespace emat
 
 using namespace emat;
@@ -1069,6 +1077,7 @@ struct emat_backend {
   // dense copy of every part's slab header (k_gather_headers): what the scalar getters read instead of the slabs
   DevBuf<uint8_t> d_headers; std::vector<uint8_t> h_headers; bool headers_current = false;
   GTreeHost gt;                     // the whole tree, when it lives in HBM (emat_tree_upload)
+  ProbeScratch probe;               // what emat_tree_probe_* / emat_tree_branch_counts work in
   BuiltTree built;                  // what emat_tree_build_usher_like made, until it is fetched (emat_tree_built_get)
   bool cfg_taper = true;            // EMAT_TICKET_TAPER: tickets of a part shrink (10 : 6 : 3 : 1 for four tickets, else n : ... : 1) instead of being equal
   int cfg_chunks = 4;               // EMAT_CHUNKS (tuning knob): tickets per part and pass (main class; measured at C4 once a ticket's release no longer wrote the L2 back, equal tickets: 2 -> 378, 3 -> 384, 6 -> 382, 10 -> 379, 16 -> 365, 32 -> 322 M moves/s; tapered: 3 -> 390, 4 -> 392, 5 -> 388; before: 1 -> 311, 2 -> 338, 3 -> 340, 4 -> 331, 8 -> 301)
@@ -2435,7 +2444,7 @@ emat_status emat_debug_gamma(emat_backend* h, int32_t mode, int32_t n, const dou
 }
 /* test hooks (header: emat_debug_pop, emat_debug_interval_op) */
 emat_status emat_debug_pop(emat_backend* h, const emat_pop_model* pm, int32_t op, int32_t n, const double* a, const double* b, double* out) {
-  if (!h || !pm || n < 0 || (op != 0 && op != 1) || (n > 0 && (!a || !b || !out))) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!h || !pm || n < 0 || op < 0 || op > 2 || (n > 0 && (!a || !b || !out))) return EMAT_ERR_INVALID_ARGUMENT;
   if (h->host_only) return fail(h, EMAT_ERR_NO_DEVICE, "host-only handle (device = -1): the engine has no CPU fallback");
   if (!bind_device(h)) return fail(h, EMAT_ERR_HIP, "hipSetDevice failed");
   if (n == 0) return EMAT_OK;
@@ -2702,5 +2711,6 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 }  // extern "C"
 
 #include "emat_gtree_host.hpp"
+#include "emat_probe_host.hpp"
 #include "emat_build_host.hpp"
 #include "emat_utree_host.hpp"

@@ -815,6 +815,54 @@ EMAT_NOTAIL EMAT_DN double pop_integral(const PopTable& p, double a, double b) {
   }
   return m_exp(skygrid_log_int_N(p, a, b));
 }
+// intensity_integral, the integral of 1 / N(t) over [a, b] (pop_model.cpp:20, 93-145, 529-531): what Tree_prober asks of a population
+// model for every cell (emat_probe_kernels.hpp).  The reference's closed forms in its order of operations; its Skygrid runs
+// log_int_N_core on minus_gamma_, so this is skygrid_log_int_N with every gamma negated (negation is exact).  Functions of their own,
+// not a parameter of the two above: the moves' kernels call those, and their code is not to change with a read-side feature.
+EMAT_D double exp_unclamped_intensity(const PopTable& p, double a, double b) { double n0 = p.p[1], g = p.p[2], t0 = p.p[0]; return -1.0 / (n0 * g) * m_exp(-g * (a - t0)) * m_expm1(-g * (b - a)); }
+EMAT_DN double skygrid_log_int_inv_N(const PopTable& p, double a, double b) {
+  const double* x = p.skygrid_x; const double* gm = p.skygrid_gamma;
+  int M = p.skygrid_num_knots - 1;
+  int ka = skygrid_interval(p, a), kb = skygrid_interval(p, b);
+  int kka = ka - 1 > 0 ? ka - 1 : 0, kkb = kb < M ? kb : M;
+  double bias = -k_inf;
+  for (int k = kka; k <= kkb; ++k) bias = bias > -gm[k] ? bias : -gm[k];
+  double result = 0.0;
+  for (int k = ka; k <= kb; ++k) {
+    double lo = k > 0 ? (a > x[k - 1] ? a : x[k - 1]) : a;
+    double hi = k <= M ? (b < x[k] ? b : x[k]) : b;
+    if (k == 0) result += m_exp(-bias + -gm[0]) * (hi - lo);
+    else if (k == M + 1) result += m_exp(-bias + -gm[M]) * (hi - lo);
+    else if (p.skygrid_type == 1) result += m_exp(-bias + -gm[k]) * (hi - lo);
+    else if (gm[k] == gm[k - 1]) result += m_exp(-bias + -gm[k]) * (hi - lo);
+    else {
+      double c_lo = (lo - x[k - 1]) / (x[k] - x[k - 1]), c_hi = (hi - x[k - 1]) / (x[k] - x[k - 1]);
+      double G_lo = (1 - c_lo) * -gm[k - 1] + c_lo * -gm[k], G_hi = (1 - c_hi) * -gm[k - 1] + c_hi * -gm[k];
+      double D = G_hi - G_lo;
+      if (D == 0.0) result += m_exp(-bias + G_lo) * (hi - lo);
+      else result += m_exp(-bias + G_lo) * (hi - lo) * (m_expm1(D) / D);
+    }
+  }
+  return m_log(result) + bias;
+}
+EMAT_NOTAIL EMAT_DN double pop_intensity_integral(const PopTable& p, double a, double b) {
+  if (p.kind == 0) return (b - a) / p.p[0];
+  if (p.kind == 1) {   // pop_model.cpp:93-145
+    double n0 = p.p[1], g = p.p[2], t0 = p.p[0], min_pop = p.p[3], t_c = p.t_c;
+    if (min_pop == 0.0) return g == 0.0 ? (b - a) / n0 : exp_unclamped_intensity(p, a, b);
+    if (g == 0.0) return (b - a) / (min_pop > n0 ? min_pop : n0);
+    double inv_min_pop = 1.0 / min_pop;
+    if (g > 0.0) {
+      if (b <= t_c) return (b - a) * inv_min_pop;
+      if (a >= t_c) return exp_unclamped_intensity(p, a, b);
+      return (t_c - a) * inv_min_pop - 1.0 / (n0 * g) * m_exp(-g * (t_c - t0)) * m_expm1(-g * (b - t_c));
+    }
+    if (a >= t_c) return (b - a) * inv_min_pop;
+    if (b <= t_c) return exp_unclamped_intensity(p, a, b);
+    return -1.0 / (n0 * g) * m_exp(-g * (a - t0)) * m_expm1(-g * (t_c - a)) + (b - t_c) * inv_min_pop;
+  }
+  return m_exp(skygrid_log_int_inv_N(p, a, b));
+}
 
 // ---- per-part coalescent prior (very_scalable_coalescent.cpp:14-79, 259-459) ----------------------------------------
 // The part stores only its window of cells [cell_first, cell_first + n_cells): outside it k_bar_p is

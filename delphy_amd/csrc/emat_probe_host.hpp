@@ -1,0 +1,193 @@
+// emat_probe_host.hpp -- host side of the tree probers (emat_probe_kernels.hpp): argument checks as the reference's constructors
+// and probers make them, the grid (with the reference's crude extension towards a root that lies before t_start), the launches.
+//
+// Included at the end of emat_backend.hip, after emat_gtree_host.hpp (gt_require).
+#ifndef EMAT_PROBE_HOST_HPP_
+#define EMAT_PROBE_HOST_HPP_
+
+namespace {
+
+constexpr int64_t k_probe_max_cells = 1 << 22;          // cells of one member, the ones prepended to reach the root included
+constexpr int64_t k_probe_max_values = 1 << 26;         // members x cells
+
+struct ProbeRequest {
+  int kind;                          // EMAT_PROBE_ANCESTORS / EMAT_PROBE_SITE_STATES
+  int32_t num_marked; const int32_t* marked; int32_t site;
+  double t_start, t_end; int32_t num_t_cells;
+};
+struct ProbePlan { ProbeGrid grid; int32_t cells_to_skip, num_members; };
+
+// The reference's argument checks, and the grid of the branch counts.
+emat_status probe_make_plan(emat_backend* h, const char* what, const ProbeRequest& q, ProbePlan& plan) {
+  const std::string w(what);
+  emat_status st = gt_require(h, true); if (st) return st;
+  GTreeHost& G = h->gt;
+  if (G.parts_live) return fail(h, EMAT_ERR_STATE, w + ": the parts are out on their slabs: emat_tree_reassemble first");
+  const int n = G.n;
+  if (q.kind == EMAT_PROBE_ANCESTORS) {
+    if (q.num_marked < 0 || (q.num_marked > 0 && !q.marked)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": num_marked must not be negative, and marked_nodes must be given");
+    for (int i = 0; i < q.num_marked; ++i)
+      if (q.marked[i] != EMAT_NO_NODE && (q.marked[i] < 0 || q.marked[i] >= n))
+        return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": node " + std::to_string(q.marked[i]) + " is neither `none` (-1) nor inside the valid range [0, " + std::to_string(n) + ")");
+  } else if (q.kind == EMAT_PROBE_SITE_STATES) {
+    if (q.site < 0 || q.site >= h->L) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": site " + std::to_string(q.site) + " is outside the valid range [0, " + std::to_string(h->L) + ")");
+    if (!h->have_ref) return fail(h, EMAT_ERR_STATE, w + ": emat_set_ref_sequence first (the root's state starts from it)");
+  } else return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": kind is neither EMAT_PROBE_ANCESTORS nor EMAT_PROBE_SITE_STATES");
+  if (!std::isfinite(q.t_start) || !std::isfinite(q.t_end) || !(q.t_start < q.t_end))
+    return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": invalid domain: need t_start < t_end, but t_start=" + std::to_string(q.t_start) + " and t_end=" + std::to_string(q.t_end));
+  if (q.num_t_cells <= 0) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": number of cells should be positive, not " + std::to_string(q.num_t_cells));
+  const int32_t members = q.kind == EMAT_PROBE_ANCESTORS ? q.num_marked + 1 : 4;
+  // ancestral_tree_prober.cpp:52-61 / site_states_tree_prober.cpp:60-69, to the letter: the same subtractions give the same doubles
+  double real_t_start = q.t_start;
+  int64_t num_cells = q.num_t_cells, cells_to_skip = 0;
+  if (q.t_start > G.h_root_t) {
+    const double cell_size = (q.t_end - q.t_start) / q.num_t_cells;
+    while (real_t_start > G.h_root_t) {
+      real_t_start -= cell_size; ++num_cells; ++cells_to_skip;
+      if (num_cells > k_probe_max_cells) break;
+    }
+  }
+  if (num_cells > k_probe_max_cells || (int64_t)members * num_cells > k_probe_max_values)
+    return fail(h, EMAT_ERR_CAPACITY, w + ": " + std::to_string(members) + " members x " + std::to_string(num_cells) + " cells (the cells it takes to reach back to the root at " + std::to_string(G.h_root_t) +
+                                       " included) is more than the prober holds (" + std::to_string(k_probe_max_cells) + " cells, " + std::to_string(k_probe_max_values) + " values)");
+  ProbeGrid g{};
+  g.x_start = real_t_start; g.num_cells = (int32_t)num_cells;
+  g.cell_size = (q.t_end - real_t_start) / g.num_cells;          // Staircase's constructor
+  g.x_end = g.x_start + g.num_cells * g.cell_size;               // Staircase::x_end()
+  int bits = 0; while (((int64_t)1 << bits) < (int64_t)n + 1) ++bits;
+  g.frac_bits = std::min(52, 61 - bits);
+  g.scale = std::ldexp(1.0, g.frac_bits); g.inv_scale = std::ldexp(1.0, -g.frac_bits);
+  plan.grid = g; plan.cells_to_skip = (int32_t)cells_to_skip; plan.num_members = members;
+  return EMAT_OK;
+}
+
+// Steps 1 and 2: the branch counts of `plan`, left in h->probe.counts on the engine's stream.
+emat_status probe_branch_counts(emat_backend* h, const ProbeRequest& q, const ProbePlan& plan) {
+  auto set_error = [&](const std::string& s) { h->set_error(s); };
+  GTreeHost& G = h->gt;
+  const int n = G.n;
+  const ProbeGrid& g = plan.grid;
+  const int32_t members = plan.num_members;
+  ProbeScratch& S = h->probe;
+  const size_t nc = (size_t)g.num_cells, values = (size_t)members * nc, nd = (size_t)members * (nc + 1);
+  HIP_TRY(S.val.alloc_roomy((size_t)n)); HIP_TRY(S.jump_a.alloc_roomy((size_t)n)); HIP_TRY(S.jump_b.alloc_roomy((size_t)n));
+  HIP_TRY(S.fix.alloc_roomy(values)); HIP_TRY(S.diff.alloc_roomy(nd)); HIP_TRY(S.counts.alloc_roomy(values)); HIP_TRY(S.status.alloc(1));
+  HIP_TRY(hipMemsetAsync(S.fix.p, 0, values * sizeof(unsigned long long), h->stream));
+  HIP_TRY(hipMemsetAsync(S.diff.p, 0, nd * sizeof(int32_t), h->stream));
+  HIP_TRY(hipMemsetAsync(S.status.p, 0, sizeof(int32_t), h->stream));
+  const dim3 per_node((unsigned)((n + 255) / 256)), b256(256);
+  const GTreeDev T = G.dev();
+  if (q.kind == EMAT_PROBE_ANCESTORS) {
+    HIP_TRY(hipMemsetAsync(S.val.p, 0xff, (size_t)n * sizeof(int32_t), h->stream));
+    if (q.num_marked > 0) {
+      HIP_TRY(S.marked.alloc_roomy((size_t)q.num_marked));
+      HIP_TRY(hipMemcpy(S.marked.p, q.marked, (size_t)q.num_marked * sizeof(int32_t), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(k_probe_marks, dim3((unsigned)((q.num_marked + 255) / 256)), b256, 0, h->stream, S.val.p, (const int32_t*)S.marked.p, (int)q.num_marked, n);
+      HIP_TRY(hipGetLastError());
+    }
+  } else {
+    hipLaunchKernelGGL(k_probe_site_flags, per_node, b256, 0, h->stream, T, q.site, (int32_t)h->ref[(size_t)q.site], S.val.p);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_probe_jump_init, per_node, b256, 0, h->stream, T, S.val.p, members - 1, S.jump_a.p);
+  HIP_TRY(hipGetLastError());
+  int32_t* cur = S.jump_a.p; int32_t* nxt = S.jump_b.p;
+  for (int64_t reach = 1; reach < n; reach *= 2) {   // after a round every jump reaches twice as far: ceil(log2 n) rounds cover any depth
+    hipLaunchKernelGGL(k_probe_jump_double, per_node, b256, 0, h->stream, n, (const int32_t*)cur, nxt);
+    HIP_TRY(hipGetLastError());
+    std::swap(cur, nxt);
+  }
+  if (q.kind == EMAT_PROBE_ANCESTORS) hipLaunchKernelGGL((k_probe_branches<false>), per_node, b256, 0, h->stream, T, g, (const int32_t*)S.val.p, (const int32_t*)cur, (int)members, S.fix.p, S.diff.p, S.status.p);
+  else hipLaunchKernelGGL((k_probe_branches<true>), per_node, b256, 0, h->stream, T, g, (const int32_t*)S.val.p, (const int32_t*)cur, (int)members, S.fix.p, S.diff.p, S.status.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_probe_counts, dim3((unsigned)members), dim3(k_wave), 0, h->stream, g, (const unsigned long long*)S.fix.p, (const int32_t*)S.diff.p, S.counts.p);
+  HIP_TRY(hipGetLastError());
+  return EMAT_OK;
+}
+
+emat_status probe_check_status(emat_backend* h, const char* what) {
+  auto set_error = [&](const std::string& s) { h->set_error(s); };
+  int32_t s = 0;
+  HIP_TRY(hipMemcpy(&s, h->probe.status.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (s == k_probe_negative_branch) return fail(h, EMAT_ERR_INTERNAL, std::string(what) + ": a node of the resident tree is earlier than its parent (the reference's add_boxcar refuses left > right)");
+  return EMAT_OK;
+}
+
+// Tree_prober (step 3) on the counts probe_branch_counts left behind; p [num_members * num_t_cells], member-major.
+emat_status probe_run(emat_backend* h, const char* what, const emat_pop_model* pm, const ProbeRequest& q, double* p) {
+  if (!h || !pm || !p) return EMAT_ERR_INVALID_ARGUMENT;
+  auto set_error = [&](const std::string& s) { h->set_error(s); };
+  const std::string w(what);
+  if (pm->kind == EMAT_POP_SKYGRID && pm->skygrid_num_knots > 0 && (!pm->skygrid_x || !pm->skygrid_gamma)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": a Skygrid model without its knots");
+  HostPopModel hp;
+  try { hp = HostPopModel::from_c(*pm); } catch (const std::exception& ex) { return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": " + ex.what()); }
+  ProbePlan plan{};
+  emat_status st = probe_make_plan(h, what, q, plan); if (st) return st;
+  st = probe_branch_counts(h, q, plan); if (st) return st;
+  ProbeScratch& S = h->probe;
+  const ProbeGrid& g = plan.grid;
+  const size_t out_values = (size_t)plan.num_members * (size_t)q.num_t_cells;
+  HIP_TRY(S.total.alloc_roomy((size_t)g.num_cells)); HIP_TRY(S.p_coalesce.alloc_roomy((size_t)g.num_cells)); HIP_TRY(S.p.alloc_roomy(out_values));
+  PopTable pt{};
+  pt.kind = hp.kind; pt.skygrid_type = hp.skygrid_type; pt.skygrid_num_knots = (int)hp.x.size();
+  for (int i = 0; i < 4; ++i) pt.p[i] = hp.p[i];
+  pt.t_c = hp.t_c;
+  if (!hp.x.empty()) {
+    HIP_TRY(S.sky_x.alloc_roomy(hp.x.size())); HIP_TRY(S.sky_g.alloc_roomy(hp.x.size()));
+    HIP_TRY(hipMemcpy(S.sky_x.p, hp.x.data(), hp.x.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(S.sky_g.p, hp.gamma.data(), hp.x.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  pt.skygrid_x = S.sky_x.p; pt.skygrid_gamma = S.sky_g.p;
+  pt.skygrid_inv_dx = (hp.x.size() >= 2 && hp.x.back() > hp.x.front()) ? (double)(hp.x.size() - 1) / (hp.x.back() - hp.x.front()) : 0.0;
+  hipLaunchKernelGGL(k_probe_cells, dim3((unsigned)((g.num_cells + 63) / 64)), dim3(64), 0, h->stream, g, pt, (int)plan.num_members, (const double*)S.counts.p, S.total.p, S.p_coalesce.p);
+  HIP_TRY(hipGetLastError());
+  // p_initial: ancestors start in "none of them"; site states in the root's state, which only the device has worked out (val[root])
+  const bool sites = q.kind == EMAT_PROBE_SITE_STATES;
+  hipLaunchKernelGGL(k_probe_chain, dim3((unsigned)((plan.num_members + 63) / 64)), dim3(64), 0, h->stream, g, (int)plan.num_members, (int)plan.cells_to_skip,
+                     (const double*)S.counts.p, (const double*)S.total.p, (const double*)S.p_coalesce.p, (int32_t)(plan.num_members - 1),
+                     sites ? (const int32_t*)(S.val.p + h->gt.h_root) : (const int32_t*)nullptr, S.p.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  st = probe_check_status(h, what); if (st) return st;
+  HIP_TRY(hipMemcpy(p, S.p.p, out_values * sizeof(double), hipMemcpyDeviceToHost));
+  return EMAT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* probe_ancestors_on_tree (header: emat_tree_probe_ancestors) */
+emat_status emat_tree_probe_ancestors(emat_backend* h, const emat_pop_model* pop_model, int32_t num_marked, const int32_t* marked_nodes,
+                                      double t_start, double t_end, int32_t num_t_cells, double* p) {
+  const ProbeRequest q{EMAT_PROBE_ANCESTORS, num_marked, marked_nodes, 0, t_start, t_end, num_t_cells};
+  return probe_run(h, "emat_tree_probe_ancestors", pop_model, q, p);
+}
+/* probe_site_states_on_tree (header: emat_tree_probe_site_states) */
+emat_status emat_tree_probe_site_states(emat_backend* h, const emat_pop_model* pop_model, int32_t site, double t_start, double t_end, int32_t num_t_cells, double* p) {
+  const ProbeRequest q{EMAT_PROBE_SITE_STATES, 0, nullptr, site, t_start, t_end, num_t_cells};
+  return probe_run(h, "emat_tree_probe_site_states", pop_model, q, p);
+}
+/* the Staircase_family the two probers hand to Tree_prober (header: emat_tree_branch_counts) */
+emat_status emat_tree_branch_counts(emat_backend* h, int32_t kind, int32_t num_marked, const int32_t* marked_nodes, int32_t site, double t_start, double t_end, int32_t num_t_cells,
+                                    int32_t* num_cells, int32_t* cells_to_skip, double* x_start, double* counts, int64_t counts_capacity) {
+  if (!h || !num_cells) return EMAT_ERR_INVALID_ARGUMENT;
+  auto set_error = [&](const std::string& s) { h->set_error(s); };
+  const ProbeRequest q{kind, num_marked, marked_nodes, site, t_start, t_end, num_t_cells};
+  ProbePlan plan{};
+  emat_status st = probe_make_plan(h, "emat_tree_branch_counts", q, plan); if (st) return st;
+  *num_cells = plan.grid.num_cells;
+  if (cells_to_skip) *cells_to_skip = plan.cells_to_skip;
+  if (x_start) *x_start = plan.grid.x_start;
+  if (!counts) return EMAT_OK;
+  const int64_t values = (int64_t)plan.num_members * plan.grid.num_cells;
+  if (counts_capacity < values) return fail(h, EMAT_ERR_BUFFER_TOO_SMALL, "emat_tree_branch_counts: " + std::to_string(values) + " values, room for " + std::to_string(counts_capacity));
+  st = probe_branch_counts(h, q, plan); if (st) return st;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  st = probe_check_status(h, "emat_tree_branch_counts"); if (st) return st;
+  HIP_TRY(hipMemcpy(counts, h->probe.counts.p, (size_t)values * sizeof(double), hipMemcpyDeviceToHost));
+  return EMAT_OK;
+}
+
+}  // extern "C"
+#endif  // EMAT_PROBE_HOST_HPP_

@@ -33,7 +33,7 @@ def library_path() -> str:
     return os.environ.get("EMAT_LIB_PATH") or os.path.join(_HERE, _LIB_NAME)
 
 
-_DEVSRC = ("emat_backend.hip", "emat_device_core.hpp", "emat_device_moves.hpp", "emat_device_spr.hpp", "emat_slab.hpp", "emat_gtree_kernels.hpp", "emat_build.hpp", "Makefile")
+_DEVSRC = ("emat_backend.hip", "emat_device_core.hpp", "emat_device_moves.hpp", "emat_device_spr.hpp", "emat_slab.hpp", "emat_gtree_kernels.hpp", "emat_build.hpp", "emat_probe_kernels.hpp", "Makefile")
 
 
 def source_build_id() -> str:
@@ -315,6 +315,8 @@ def load_library():
         "emat_tree_repartition_range": [B, i32, P(i32), P(i32), P(i32), P(i32), i32, P(u64), P(_PopModelC), dbl, i32, i32],
         "emat_tree_get_root_deltas": [B, P(i32), P(i32), P(C.c_uint8), P(C.c_uint8), i32], "emat_tree_gather_local": [B, i32, P(i32), P(C.c_uint8), P(C.c_uint8)],
         "emat_tree_export_nodes": [B, P(C.c_uint8), u64, P(u64)], "emat_tree_apply_nodes": [B, P(C.c_uint8), u64], "emat_tree_reassemble_end": [B],
+        "emat_tree_probe_ancestors": [B, P(_PopModelC), i32, P(i32), dbl, dbl, i32, P(dbl)], "emat_tree_probe_site_states": [B, P(_PopModelC), i32, dbl, dbl, i32, P(dbl)],
+        "emat_tree_branch_counts": [B, i32, i32, P(i32), i32, dbl, dbl, i32, P(i32), P(i32), P(dbl), P(dbl), i64],
         "emat_run_note_device_reassembled": [R, i32, P(i32), P(C.c_uint8)], "emat_run_set_paranoid": [R, i32], "emat_run_set_reference_remainder": [R, i32],
     }
     M = C.c_void_p
@@ -648,6 +650,37 @@ class EmatBackend:
         t.root = v.root
         return t.trimmed(), ref
 
+    # ---- the tree probers on the resident tree (include/emat_backend.h: emat_tree_probe_*, emat_tree_branch_counts) ----
+    def tree_probe_ancestors(self, pop: PopModel, marked_nodes, t_start: float, t_end: float, num_t_cells: int) -> np.ndarray:
+        """probe_ancestors_on_tree: p [len(marked_nodes) + 1][num_t_cells]; the last member is "none of them", -1 marks nothing."""
+        mk = np.ascontiguousarray(marked_nodes, np.int32).reshape(-1)
+        out = np.zeros((mk.shape[0] + 1, max(num_t_cells, 1)))      # (a bad cell count is the library's to refuse)
+        m = pop.c_struct()
+        self._ck(self._lib.emat_tree_probe_ancestors(self._h, C.byref(m), int(mk.shape[0]), _ptr(mk, C.c_int32) if mk.shape[0] else None, t_start, t_end, num_t_cells,
+                                                     _ptr(out, C.c_double)), "emat_tree_probe_ancestors")
+        return out
+
+    def tree_probe_site_states(self, pop: PopModel, site: int, t_start: float, t_end: float, num_t_cells: int) -> np.ndarray:
+        """probe_site_states_on_tree: p [4][num_t_cells], states A, C, G, T."""
+        out = np.zeros((4, max(num_t_cells, 1)))
+        m = pop.c_struct()
+        self._ck(self._lib.emat_tree_probe_site_states(self._h, C.byref(m), site, t_start, t_end, num_t_cells, _ptr(out, C.c_double)), "emat_tree_probe_site_states")
+        return out
+
+    def tree_branch_counts(self, t_start: float, t_end: float, num_t_cells: int, marked_nodes=None, site: Optional[int] = None):
+        """The branch counts a prober hands to Tree_prober -- of the ancestral prober when `marked_nodes` is given, else of the site-state
+        prober for `site`: (counts [members][cells], cells_to_skip, x_start), the cells prepended to reach the root included."""
+        if (marked_nodes is None) == (site is None):
+            raise ValueError("give marked_nodes or site")
+        kind = 0 if site is None else 1
+        mk = np.ascontiguousarray([] if marked_nodes is None else marked_nodes, np.int32).reshape(-1)
+        args = (kind, int(mk.shape[0]), _ptr(mk, C.c_int32) if mk.shape[0] else None, 0 if site is None else site, t_start, t_end, num_t_cells)
+        n, skip, x0 = C.c_int32(), C.c_int32(), C.c_double()
+        self._ck(self._lib.emat_tree_branch_counts(self._h, *args, C.byref(n), C.byref(skip), C.byref(x0), None, 0), "emat_tree_branch_counts")
+        out = np.zeros((mk.shape[0] + 1 if kind == 0 else 4, n.value))
+        self._ck(self._lib.emat_tree_branch_counts(self._h, *args, C.byref(n), C.byref(skip), C.byref(x0), _ptr(out, C.c_double), out.size), "emat_tree_branch_counts")
+        return out, int(skip.value), float(x0.value)
+
     def tree_counters(self):
         """(growths of the cut-state pools, growths of the list heaps, cut-point states that needed the large kernel) of the
         HBM-resident tree: testing aid."""
@@ -736,7 +769,7 @@ class EmatBackend:
         return float(v.value)
 
     def debug_pop(self, pop: PopModel, op: int, a, b) -> np.ndarray:
-        """Test hook: the device's pop_at_time (op 0) / pop_integral (op 1), point by point."""
+        """Test hook: the device's pop_at_time (op 0) / pop_integral (op 1) / intensity_integral (op 2), point by point."""
         a = np.ascontiguousarray(a, np.float64); b = np.ascontiguousarray(b, np.float64); out = np.zeros_like(a)
         m = pop.c_struct(); dp = C.POINTER(C.c_double)
         self._ck(self._lib.emat_debug_pop(self._h, C.byref(m), op, a.shape[0], a.ctypes.data_as(dp), b.ctypes.data_as(dp), out.ctypes.data_as(dp)), "emat_debug_pop")

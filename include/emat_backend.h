@@ -257,6 +257,34 @@ emat_status emat_tree_repartition(emat_backend* h, int32_t num_parts, const int3
 /* `site` / `from` / `to` [capacity] receive the changes of the reference sequence (old state, new state); any of the
  * output arguments may be NULL / 0 when the caller reads the sequence through emat_tree_download instead. */
 emat_status emat_tree_reassemble(emat_backend* h, int32_t* num_root_deltas, int32_t* site, uint8_t* from, uint8_t* to, int32_t capacity);
+/* ---- the tree probers on the resident tree: where, over time, a fresh sample would coalesce --------------------------------
+ * They read the tree as it stands in HBM after emat_tree_upload or emat_tree_reassemble (with the run driver: between
+ * emat_run_reassemble and the next emat_run_repartition) and return (members x cells) doubles; the tree itself stays where it
+ * is.  While the parts are out on their slabs they fail with EMAT_ERR_STATE, as emat_tree_download does.  The time grid is the
+ * reference's: num_t_cells cells of equal size over [t_start, t_end); when t_start lies after the root's time, cells of that size
+ * are prepended until the root is covered (`cells_to_skip`), computed on but not returned.  Bad arguments are
+ * EMAT_ERR_INVALID_ARGUMENT with the reference's complaint in emat_last_error: a site outside [0, num_sites), a marked node that
+ * is neither -1 nor a node, t_end <= t_start, num_t_cells < 1, a population model its constructor refuses; a grid of more than
+ * 2^22 cells or 2^26 values is EMAT_ERR_CAPACITY.  Results are bit-for-bit the same from call to call.
+ *
+ *   emat_tree_probe_ancestors    probe_ancestors_on_tree (core/ancestral_tree_prober.cpp:31-77): p[i][c] = probability that the
+ *                                closest marked ancestor of a sample taken at the end of cell c is marked_nodes[i]; the last
+ *                                member, i = num_marked, is "none of them".  -1 marks nothing (its member stays 0); of a node
+ *                                given twice the first entry counts.
+ *   emat_tree_probe_site_states  probe_site_states_on_tree (core/site_states_tree_prober.cpp:43-99): p[s][c] = probability that
+ *                                the sample carries state s (A, C, G, T) at `site`, starting from the root's state.
+ *   emat_tree_branch_counts      the Staircase_family of branch counts either prober hands to Tree_prober (core/tree_prober.h;
+ *                                ancestral_tree_prober.cpp:7-29 / site_states_tree_prober.cpp:5-41 on core/staircase.cpp's
+ *                                add_boxcar / add_trapezoid): counts[member][cell] over ALL *num_cells cells, the *cells_to_skip
+ *                                prepended ones included, the first starting at *x_start.  With counts = NULL only the three
+ *                                sizes are returned.  `kind` selects the prober; the arguments of the other one are ignored. */
+typedef enum emat_probe_kind { EMAT_PROBE_ANCESTORS = 0, EMAT_PROBE_SITE_STATES = 1 } emat_probe_kind;
+emat_status emat_tree_probe_ancestors(emat_backend* h, const emat_pop_model* pop_model, int32_t num_marked, const int32_t* marked_nodes /* [num_marked] */,
+                                      double t_start, double t_end, int32_t num_t_cells, double* p /* [(num_marked + 1) * num_t_cells], member-major */);
+emat_status emat_tree_probe_site_states(emat_backend* h, const emat_pop_model* pop_model, int32_t site, double t_start, double t_end, int32_t num_t_cells,
+                                        double* p /* [4 * num_t_cells], member-major */);
+emat_status emat_tree_branch_counts(emat_backend* h, int32_t kind, int32_t num_marked, const int32_t* marked_nodes, int32_t site, double t_start, double t_end, int32_t num_t_cells,
+                                    int32_t* num_cells, int32_t* cells_to_skip, double* x_start, double* counts /* [members * *num_cells] or NULL */, int64_t counts_capacity);
 /* One run over several processes, one GPU each, EVERY one with the whole tree in its HBM (the tree is a few tens of MB; what
  * is worth sharding is the moves).  Every process cuts the same partition and calls emat_tree_repartition_range with its own
  * block [part_lo, part_hi) of the parts (backend part id = part - part_lo): the sequence states at the cut points and the
@@ -418,8 +446,9 @@ emat_status emat_last_kernel_ms(emat_backend* h, double* ms, int32_t* num_parts_
  * whose source is not part of the reference tree; tests/test_parity_gpu.py sweeps them over tests/golden/gamma_q.json. */
 emat_status emat_debug_gamma(emat_backend* h, int32_t mode, int32_t n, const double* a, const double* x_or_q, double* out);
 /* The device's population-model routines, point by point (reference pop_model.cpp:18-145, 247-330): op 0: out[i] = N(a[i])
- * (pop_at_time); op 1: out[i] = integral of N over [a[i], b[i]] (pop_integral).  tests/ sweeps them over the reference's
- * own expectations (tests/golden/reference_expectations.json). */
+ * (pop_at_time); op 1: out[i] = integral of N over [a[i], b[i]] (pop_integral); op 2: integral of 1 / N over [a[i], b[i]]
+ * (intensity_integral, what the tree probers use).  tests/ sweeps them over the reference's own expectations
+ * (tests/golden/reference_expectations.json). */
 emat_status emat_debug_pop(emat_backend* h, const emat_pop_model* pop_model, int32_t op, int32_t n, const double* a, const double* b, double* out);
 /* The moves' own tree queries on one resident part, query by query (reference phylo_tree.cpp:204-280, 292-299): op 0: out[i] =
  * find_MRCA_of(a[i], b[i]); op 1: out[i] = descends_from(a[i], b[i]) (0 / 1); -1 stands for k_no_node.  tests/ runs them over the
