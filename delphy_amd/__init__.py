@@ -11,6 +11,7 @@ from .engine import (  # noqa: F401
     EmatMultiRun,
     EmatRun,
     FlatTree,
+    MccTree,
     PopModel,
     SynthParams,
     TipDescs,

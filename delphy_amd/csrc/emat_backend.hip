@@ -868,6 +868,7 @@ __global__ void k_debug_interval_op(int op, const IvRec* A, int nA, const IvRec*
 #include "emat_gtree_kernels.hpp"   // the whole tree in HBM: cutting it into part slabs and gathering the parts back
 #include "emat_build.hpp"           // initial-tree construction: the graft loop as a kernel, the finishing passes on the host
 #include "emat_probe_kernels.hpp"   // the tree probers on the resident tree: lineage and site-state prevalence over time
+#include "emat_mcc_kernels.hpp"     // sampled trees kept in HBM, and the maximum-clade-credibility tree derived from them
 namespace emat {
 
 // =================================================================================================
@@ -997,6 +998,20 @@ struct ProbeScratch {
   DevBuf<double> counts, total, p_coalesce, p, sky_x, sky_g;
 };
 
+// The store of sampled trees and what emat_mcc_derive works in (emat_mcc_kernels.hpp, emat_mcc_host.hpp).  The store is sized by
+// emat_tree_samples_reserve; the derivation's buffers are allocated at the first call and grown on demand.
+struct MccHost {
+  int32_t capacity = 0, n = 0, count = 0;             // slots, nodes of every sample, slots in use
+  DevBuf<int32_t> parent, c0, c1, root; DevBuf<double> t;
+  std::vector<uint8_t> is_tip;                         // of sample 0: every later sample has the same tips
+  DevBuf<unsigned long long> fp, keys; DevBuf<int32_t> ntips, arrive, corr, counts, hist, info, num_exact; DevBuf<uint8_t> exact;
+  DevBuf<double> support, t_out, t_mrca;
+  MccTable table{}; int32_t table_regrows = 0; int table_log2_hint = 0;   // the table of clade counts of the last derivation; the size it ended with is where the next one starts
+  int32_t derived_M = 0, derived_n = 0;                // the (M x n) correspondence table of the last derivation is valid
+  template <class T> static void drop(DevBuf<T>& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 0; }
+  void release() { drop(parent); drop(c0); drop(c1); drop(root); drop(t); drop(fp); drop(keys); drop(ntips); drop(arrive); drop(corr); drop(counts); drop(hist); drop(exact); capacity = 0; count = 0; derived_M = 0; table_log2_hint = 0; }
+};
+
 }  // namespace emat
 
 using namespace emat;
@@ -1078,6 +1093,8 @@ struct emat_backend {
   DevBuf<uint8_t> d_headers; std::vector<uint8_t> h_headers; bool headers_current = false;
   GTreeHost gt;                     // the whole tree, when it lives in HBM (emat_tree_upload)
   ProbeScratch probe;               // what emat_tree_probe_* / emat_tree_branch_counts work in
+  MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
+  int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs
   BuiltTree built;                  // what emat_tree_build_usher_like made, until it is fetched (emat_tree_built_get)
   bool cfg_taper = true;            // EMAT_TICKET_TAPER: tickets of a part shrink (10 : 6 : 3 : 1 for four tickets, else n : ... : 1) instead of being equal
   int cfg_chunks = 4;               // EMAT_CHUNKS (tuning knob): tickets per part and pass (main class; measured at C4 once a ticket's release no longer wrote the L2 back, equal tickets: 2 -> 378, 3 -> 384, 6 -> 382, 10 -> 379, 16 -> 365, 32 -> 322 M moves/s; tapered: 3 -> 390, 4 -> 392, 5 -> 388; before: 1 -> 311, 2 -> 338, 3 -> 340, 4 -> 331, 8 -> 301)
@@ -1865,6 +1882,7 @@ emat_status emat_backend_destroy(emat_backend* h) {
 emat_status emat_set_option(emat_backend* h, const char* key, const char* value) {
   if (!h || !key || !value) return EMAT_ERR_INVALID_ARGUMENT;
   if (strcmp(key, "debug_fail_gather") == 0) { h->cfg_debug_fail_gather = atoi(value) != 0; return EMAT_OK; }   // (a test hook that is armed in the middle of a run)
+  if (strcmp(key, "mcc_table_log2") == 0) { h->cfg_mcc_table_log2 = std::max(0, std::min(32, atoi(value))); return EMAT_OK; }   // (read by every emat_mcc_derive)
   if (h->slabs_on_device) return fail(h, EMAT_ERR_STATE, "emat_set_option: options are set before the first launch");
   const std::string k(key);
   const char* e = value;
@@ -2712,5 +2730,6 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 
 #include "emat_gtree_host.hpp"
 #include "emat_probe_host.hpp"
+#include "emat_mcc_host.hpp"
 #include "emat_build_host.hpp"
 #include "emat_utree_host.hpp"

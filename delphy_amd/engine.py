@@ -33,7 +33,7 @@ def library_path() -> str:
     return os.environ.get("EMAT_LIB_PATH") or os.path.join(_HERE, _LIB_NAME)
 
 
-_DEVSRC = ("emat_backend.hip", "emat_device_core.hpp", "emat_device_moves.hpp", "emat_device_spr.hpp", "emat_slab.hpp", "emat_gtree_kernels.hpp", "emat_build.hpp", "emat_probe_kernels.hpp", "Makefile")
+_DEVSRC = ("emat_backend.hip", "emat_device_core.hpp", "emat_device_moves.hpp", "emat_device_spr.hpp", "emat_slab.hpp", "emat_gtree_kernels.hpp", "emat_build.hpp", "emat_probe_kernels.hpp", "emat_mcc_kernels.hpp", "Makefile")
 
 
 def source_build_id() -> str:
@@ -77,6 +77,32 @@ class _FlatTreeC(C.Structure):
 class _PopModelC(C.Structure):
     _fields_ = [("kind", C.c_int32), ("p", C.c_double * 4), ("skygrid_type", C.c_int32), ("skygrid_num_knots", C.c_int32),
                 ("skygrid_x", C.POINTER(C.c_double)), ("skygrid_gamma", C.POINTER(C.c_double))]
+
+
+class _MccResultC(C.Structure):
+    _fields_ = [("master_position", C.c_int32), ("master_index", C.c_int32), ("log_cc", C.POINTER(C.c_double)),
+                ("parent", C.POINTER(C.c_int32)), ("child0", C.POINTER(C.c_int32)), ("child1", C.POINTER(C.c_int32)), ("root", C.c_int32),
+                ("support", C.POINTER(C.c_double)), ("t", C.POINTER(C.c_double)), ("t_mrca", C.POINTER(C.c_double)), ("num_exact", C.POINTER(C.c_int32)),
+                ("num_distinct_clades", C.c_int32), ("table_regrows", C.c_int32), ("table_slots", C.c_int64)]
+
+
+@dataclass
+class MccTree:
+    """What emat_mcc_derive returns (include/emat_backend.h: emat_mcc_result; reference Mcc_tree)."""
+    master: int                 # which of the chosen samples is the master ...
+    master_index: int           # ... and its slot in the store
+    log_cc: np.ndarray          # [count] log clade credibility of every chosen sample
+    parent: np.ndarray          # the MCC tree's topology = the master's
+    child0: np.ndarray
+    child1: np.ndarray
+    root: int
+    support: np.ndarray         # [n] posterior support = num_exact / count
+    t: np.ndarray               # [n] mean time over the samples that have the node's clade
+    t_mrca: np.ndarray          # [n] mean time of the MRCA of the node's tips over all samples
+    num_exact: np.ndarray       # [n] samples that have the node's clade
+    num_distinct_clades: int
+    table_regrows: int
+    table_slots: int
 
 
 class _TipDescsC(C.Structure):
@@ -317,6 +343,9 @@ def load_library():
         "emat_tree_export_nodes": [B, P(C.c_uint8), u64, P(u64)], "emat_tree_apply_nodes": [B, P(C.c_uint8), u64], "emat_tree_reassemble_end": [B],
         "emat_tree_probe_ancestors": [B, P(_PopModelC), i32, P(i32), dbl, dbl, i32, P(dbl)], "emat_tree_probe_site_states": [B, P(_PopModelC), i32, dbl, dbl, i32, P(dbl)],
         "emat_tree_branch_counts": [B, i32, i32, P(i32), i32, dbl, dbl, i32, P(i32), P(i32), P(dbl), P(dbl), i64],
+        "emat_tree_samples_reserve": [B, i32], "emat_tree_sample_push": [B, P(i32)], "emat_tree_sample_push_flat": [B, i32, P(i32), P(i32), P(i32), P(dbl), i32, P(i32)],
+        "emat_tree_samples_count": [B, P(i32), P(i32), P(i32)], "emat_tree_samples_clear": [B], "emat_tree_sample_get": [B, i32, P(i32), P(i32), P(i32), P(dbl), P(i32)],
+        "emat_mcc_derive": [B, i32, i32, i32, u64, P(_MccResultC)], "emat_mcc_get_correspondence": [B, i32, P(i32), P(C.c_uint8)],
         "emat_run_note_device_reassembled": [R, i32, P(i32), P(C.c_uint8)], "emat_run_set_paranoid": [R, i32], "emat_run_set_reference_remainder": [R, i32],
     }
     M = C.c_void_p
@@ -680,6 +709,66 @@ class EmatBackend:
         out = np.zeros((mk.shape[0] + 1 if kind == 0 else 4, n.value))
         self._ck(self._lib.emat_tree_branch_counts(self._h, *args, C.byref(n), C.byref(skip), C.byref(x0), _ptr(out, C.c_double), out.size), "emat_tree_branch_counts")
         return out, int(skip.value), float(x0.value)
+
+    # ---- sampled trees kept in HBM and the MCC tree derived from them (include/emat_backend.h: emat_tree_sample_*, emat_mcc_*) ----
+    def tree_samples_reserve(self, capacity: int) -> None:
+        """Room for `capacity` samples of the resident tree's node count."""
+        self._ck(self._lib.emat_tree_samples_reserve(self._h, capacity), "emat_tree_samples_reserve")
+
+    def tree_sample_push(self) -> int:
+        """Snapshot of the resident tree's topology and node times into the next slot, device to device; returns the slot."""
+        i = C.c_int32(-1)
+        self._ck(self._lib.emat_tree_sample_push(self._h, C.byref(i)), "emat_tree_sample_push")
+        return int(i.value)
+
+    def tree_sample_push_flat(self, parent, child0, child1, t, root: int) -> int:
+        """The same from host arrays (checked: node count, binary, one root, consistent links, the tips of sample 0)."""
+        pa = np.ascontiguousarray(parent, np.int32); a0 = np.ascontiguousarray(child0, np.int32); a1 = np.ascontiguousarray(child1, np.int32); tt = np.ascontiguousarray(t, np.float64)
+        if not (pa.shape == a0.shape == a1.shape == tt.shape and pa.ndim == 1):
+            raise ValueError("parent, child0, child1 and t must be one-dimensional and of one length")
+        i = C.c_int32(-1)
+        self._ck(self._lib.emat_tree_sample_push_flat(self._h, int(pa.shape[0]), _ptr(pa, C.c_int32), _ptr(a0, C.c_int32), _ptr(a1, C.c_int32), _ptr(tt, C.c_double), int(root), C.byref(i)), "emat_tree_sample_push_flat")
+        return int(i.value)
+
+    def tree_samples_count(self) -> int:
+        return self.tree_samples_info()[0]
+
+    def tree_samples_info(self):
+        """(samples held, capacity in samples, nodes per sample)."""
+        c, cap, n = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self._lib.emat_tree_samples_count(self._h, C.byref(c), C.byref(cap), C.byref(n)), "emat_tree_samples_count")
+        return int(c.value), int(cap.value), int(n.value)
+
+    def tree_samples_clear(self) -> None:
+        self._ck(self._lib.emat_tree_samples_clear(self._h), "emat_tree_samples_clear")
+
+    def tree_sample_get(self, index: int):
+        """(parent, child0, child1, t, root) of one slot."""
+        n = self.tree_samples_info()[2]
+        parent = np.zeros(n, np.int32); c0 = np.zeros(n, np.int32); c1 = np.zeros(n, np.int32); t = np.zeros(n); root = C.c_int32(-1)
+        self._ck(self._lib.emat_tree_sample_get(self._h, index, _ptr(parent, C.c_int32), _ptr(c0, C.c_int32), _ptr(c1, C.c_int32), _ptr(t, C.c_double), C.byref(root)), "emat_tree_sample_get")
+        return parent, c0, c1, t, int(root.value)
+
+    def mcc_derive(self, first: int = 0, count: Optional[int] = None, stride: int = 1, seed: int = 0) -> "MccTree":
+        """derive_mcc_tree over the samples first, first + stride, ... (`count` of them; default: as many as the store has from `first`)."""
+        held, _, n = self.tree_samples_info()
+        if count is None:
+            count = max(0, (held - first + stride - 1) // stride) if stride >= 1 and first >= 0 else 0
+        m = max(count, 1)
+        r = MccTree(0, 0, np.zeros(m), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), -1, np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n, np.int32), 0, 0, 0)
+        c = _MccResultC(0, 0, _ptr(r.log_cc, C.c_double), _ptr(r.parent, C.c_int32), _ptr(r.child0, C.c_int32), _ptr(r.child1, C.c_int32), -1,
+                        _ptr(r.support, C.c_double), _ptr(r.t, C.c_double), _ptr(r.t_mrca, C.c_double), _ptr(r.num_exact, C.c_int32), 0, 0, 0)
+        self._ck(self._lib.emat_mcc_derive(self._h, first, count, stride, seed & (2 ** 64 - 1), C.byref(c)), "emat_mcc_derive")
+        r.master, r.master_index, r.root = int(c.master_position), int(c.master_index), int(c.root)
+        r.num_distinct_clades, r.table_regrows, r.table_slots = int(c.num_distinct_clades), int(c.table_regrows), int(c.table_slots)
+        return r
+
+    def mcc_correspondence(self, k: int):
+        """(node_in_sample [n], is_exact [n] bool) of the k-th chosen sample of the last mcc_derive."""
+        n = self.tree_samples_info()[2]
+        node = np.zeros(n, np.int32); ex = np.zeros(n, np.uint8)
+        self._ck(self._lib.emat_mcc_get_correspondence(self._h, k, _ptr(node, C.c_int32), _ptr(ex, C.c_uint8)), "emat_mcc_get_correspondence")
+        return node, ex.astype(bool)
 
     def tree_counters(self):
         """(growths of the cut-state pools, growths of the list heaps, cut-point states that needed the large kernel) of the

@@ -119,6 +119,7 @@ emat_status emat_backend_destroy(emat_backend* h);
  *   "no_uniform_sites" (1: the moves read the per-site partition and rate arrays even when the model is the reference's default of one
  *   site partition and nu_l == 1 everywhere, where the answers are known without a load: the A/B of that short cut, round 6),
  *   "debug_fail_gather" (1: the next deferred gather of the device-resident tree reports an inconsistency; may be set at any time);
+ *   "mcc_table_log2" (log2 of the slots emat_mcc_derive's table of clade counts starts with, 0 = four per node: a small value makes it grow; may be set at any time);
  *   profiling builds: "fn_min_lists", "phase_extra". */
 emat_status emat_set_option(emat_backend* h, const char* key, const char* value);
 /* Size of the library's host thread pool (per process, before its first parallel loop; 0 = default: min(cores, 16)). */
@@ -285,6 +286,73 @@ emat_status emat_tree_probe_site_states(emat_backend* h, const emat_pop_model* p
                                         double* p /* [4 * num_t_cells], member-major */);
 emat_status emat_tree_branch_counts(emat_backend* h, int32_t kind, int32_t num_marked, const int32_t* marked_nodes, int32_t site, double t_start, double t_end, int32_t num_t_cells,
                                     int32_t* num_cells, int32_t* cells_to_skip, double* x_start, double* counts /* [members * *num_cells] or NULL */, int64_t counts_capacity);
+/* ---- sampled trees kept in HBM, and the maximum-clade-credibility (MCC) tree derived from them ------------------------------
+ * What a front end shows of the RUN.  The reference keeps copies of the run's tree on the host (tools/delphy_ui.cpp:770-773) and
+ * derives the MCC tree from them with derive_mcc_tree (core/mcc_tree.cpp:58-156; tools/delphy_ui.cpp:784, tools/delphy_mcc.cpp).
+ * All that needs of a sample is its topology and node times, 20 bytes a node, which the resident tree already has in HBM: a
+ * sample is a device-to-device snapshot of those into a slot of a store, and every step of the derivation runs over
+ * (samples x nodes) on the device.
+ *
+ * When: emat_tree_sample_push reads the resident tree as the probers do -- after emat_tree_upload or emat_tree_reassemble, with
+ * the run driver between emat_run_reassemble and the next emat_run_repartition; while the parts are out on their slabs it fails
+ * with EMAT_ERR_STATE.  It is queued on the engine's stream and returns at once.  Everything else here touches only the store
+ * and may be called at any time, also while the parts are out (their launches queue behind the moves on the same stream).
+ * The store belongs to ONE node count: after emat_tree_upload of a tree with another node count every push fails with
+ * EMAT_ERR_STATE until emat_tree_samples_clear, which re-binds the store to the new count.  Samples must have the SAME nodes as
+ * tips (the reference assumes tips keep their indices across base trees, mcc_tree.cpp:118-124; the engine's moves keep them).
+ * With several processes every rank holds the whole tree after a reassemble; rank 0 keeps the store alone, as with the probers.
+ * A handle without a device gets EMAT_ERR_NO_DEVICE: there is no CPU path.
+ *
+ *   emat_tree_samples_reserve   room for `capacity` samples of the resident tree's node count n: capacity x n x 20 bytes, and it
+ *                               checks that the 21 bytes per sample and node a derivation over all of them works in are there
+ *                               too.  More than the device has free is EMAT_ERR_CAPACITY with the sizes in emat_last_error.
+ *                               A store that holds samples is not resized (EMAT_ERR_STATE): clear it first.
+ *   emat_tree_sample_push       tree_snapshots.push_back(tree) (delphy_ui.cpp:770): parent, children, times and root of the
+ *                               resident tree into the next slot; *index (may be NULL) receives the slot.  A full store is
+ *                               EMAT_ERR_CAPACITY: nothing is evicted.
+ *   emat_tree_sample_push_flat  the same from host arrays of num_nodes nodes (trees read from a file, as tools/delphy_mcc.cpp does).
+ *                               EMAT_ERR_INVALID_ARGUMENT unless num_nodes is the store's, the tree is binary with one root and
+ *                               consistent links, every node is below the root, and the tips are sample 0's tips.
+ *   emat_tree_samples_count     slots in use, slots, nodes per sample (any may be NULL)
+ *   emat_tree_samples_clear     forgets every sample (and the last derivation's correspondence table); keeps the room
+ *   emat_tree_sample_get        one slot back to the host (any array may be NULL)
+ *   emat_mcc_derive             derive_mcc_tree over the M = count samples first, first + stride, ... (burn-in and thinning are
+ *                               the caller's: delphy_ui.cpp:770-784).  Tip fingerprints are 64 bits of a counter-based generator of
+ *                               (seed, node) where the reference draws 64 bits from its bit generator (mcc_tree.cpp:70-76): two
+ *                               different clades share one with probability ~ (M n)^2 / 2^65 (3e-4 at M = 1000, n = 1e5), as
+ *                               there.  log_cc[k] is the sum of hist[c] (log c - log M) over c ascending, hist[c] = number of inner
+ *                               nodes of sample k whose clade is in c samples (:78-103 sums the same terms in node order); the
+ *                               master is the first maximum (:105-108).  support / t / t_mrca are the sums over the samples in
+ *                               sample order of Mcc_tree::calculate_derived_quantities (:158-179): the same doubles.  Nothing
+ *                               but the fingerprints depends on `seed`, and the same arguments give the same bits.
+ *                               EMAT_ERR_INVALID_ARGUMENT: count < 1, stride < 1, a sample outside the store.
+ *   emat_mcc_get_correspondence corresponding_node_to (mcc_tree.h:91-98): for the k-th chosen sample of the last derivation and
+ *                               every MCC node, the MRCA in that sample of the tips below the MCC node (mcc_tree.cpp:118-147), and
+ *                               whether it is exactly that clade.  The (M x n) table stays in HBM until the next derive / clear. */
+typedef struct emat_mcc_result {
+  int32_t master_position;   /* out: which of the `count` chosen samples is the master ... */
+  int32_t master_index;      /* out: ... and its slot, first + master_position * stride */
+  double* log_cc;            /* [count] log clade credibility of every chosen sample, or NULL */
+  int32_t* parent;           /* [n] the MCC tree's topology = the master's; any of these may be NULL */
+  int32_t* child0;           /* [n] */
+  int32_t* child1;           /* [n] */
+  int32_t root;              /* out */
+  double* support;           /* [n] posterior_support = num_exact / count */
+  double* t;                 /* [n] mean time of the corresponding nodes that match exactly */
+  double* t_mrca;            /* [n] mean time of all corresponding nodes */
+  int32_t* num_exact;        /* [n] in how many chosen samples the MCC node's clade occurs */
+  int32_t num_distinct_clades;   /* out: keys in the table of clade counts (tips included) */
+  int32_t table_regrows;     /* out: how often that table was quadrupled and refilled */
+  int64_t table_slots;       /* out: its final size */
+} emat_mcc_result;
+emat_status emat_tree_samples_reserve(emat_backend* h, int32_t capacity);
+emat_status emat_tree_sample_push(emat_backend* h, int32_t* index);
+emat_status emat_tree_sample_push_flat(emat_backend* h, int32_t num_nodes, const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* t, int32_t root, int32_t* index);
+emat_status emat_tree_samples_count(emat_backend* h, int32_t* count, int32_t* capacity, int32_t* num_nodes);
+emat_status emat_tree_samples_clear(emat_backend* h);
+emat_status emat_tree_sample_get(emat_backend* h, int32_t index, int32_t* parent, int32_t* child0, int32_t* child1, double* t, int32_t* root);
+emat_status emat_mcc_derive(emat_backend* h, int32_t first, int32_t count, int32_t stride, uint64_t seed, emat_mcc_result* out);
+emat_status emat_mcc_get_correspondence(emat_backend* h, int32_t k, int32_t* node_in_sample /* [n] */, uint8_t* is_exact /* [n] */);
 /* One run over several processes, one GPU each, EVERY one with the whole tree in its HBM (the tree is a few tens of MB; what
  * is worth sharding is the moves).  Every process cuts the same partition and calls emat_tree_repartition_range with its own
  * block [part_lo, part_hi) of the parts (backend part id = part - part_lo): the sequence states at the cut points and the

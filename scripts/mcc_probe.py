@@ -1,0 +1,82 @@
+"""What the store of sampled trees and the MCC derivation cost at full size (config C4, 199 999 nodes): one JSON line.
+
+Medians of >= 20 calls in one process, synchronise included:
+  * emat_tree_sample_push against the two calls it replaces, emat_tree_get_topology and emat_tree_download, on the same build, each both
+    right after a reassemble (a push per cycle, as a sampler meets it) and as repeated calls on one tree;
+  * emat_mcc_derive at M = 32, 256 and 1 000 samples (--samples), the samples pushed after as many cycles of the run driver;
+  * with --host-model: tests/mcc_model.py (a), derive_mcc_tree to the letter in Python, on the first 32 samples on the host.
+
+    python scripts/mcc_probe.py [--samples 32,256,1000] [--moves-per-part 50] [--host-model] > profiles/mcc_probe_latest.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import delphy_amd as d  # noqa: E402
+from delphy_amd.scenarios import make_scenario  # noqa: E402
+
+
+def median_ms(f, calls):
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter(); f(); ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="C4")
+    ap.add_argument("--samples", default="32,256,1000")
+    ap.add_argument("--parts", type=int, default=8192)
+    ap.add_argument("--moves-per-part", type=int, default=50)
+    ap.add_argument("--calls", type=int, default=21)
+    ap.add_argument("--host-model", action="store_true")
+    a = ap.parse_args()
+    sizes = sorted(int(x) for x in a.samples.split(","))
+    sc = make_scenario(a.config)
+    b = d.EmatBackend(sc.num_sites)
+    run = d.EmatRun(b, sc.tree, sc.ref, 5)
+    run.set_num_parts(a.parts); run.set_hky(sc.mu, sc.kappa, sc.pi); run.set_pop_model(sc.pop); run.set_device_tree(True)
+    out = {"config": a.config, "num_nodes": int(sc.tree.num_nodes), "emat_build_id": d.library_build_id(), "date": time.strftime("%Y-%m-%d"), "calls_per_median": a.calls,
+           "parts": a.parts, "moves_per_part_and_cycle": a.moves_per_part}
+    t_push, t_topo = [], []
+    try:
+        for cycle in range(sizes[-1]):
+            run.repartition()
+            if cycle == 0: b.tree_samples_reserve(sizes[-1] + a.calls)
+            run.run_moves(a.parts * a.moves_per_part); b.synchronize()
+            run.reassemble(); b.synchronize()
+            t0 = time.perf_counter(); b.tree_sample_push(); b.synchronize(); t1 = time.perf_counter()
+            t_push.append((t1 - t0) * 1e3)
+            if cycle < 32:
+                b.tree_topology(); t_topo.append((time.perf_counter() - t1) * 1e3)
+            if cycle % 100 == 99: print("cycle", cycle + 1, file=sys.stderr, flush=True)
+        out["push_after_reassemble_ms"] = float(np.median(t_push)); out["get_topology_after_reassemble_ms"] = float(np.median(t_topo))
+        out["push_repeated_ms"] = median_ms(lambda: (b.tree_sample_push(), b.synchronize()), a.calls)
+        out["get_topology_repeated_ms"] = median_ms(b.tree_topology, a.calls)
+        out["tree_download_ms"] = median_ms(b.tree_download, a.calls)
+        out["derive"] = []
+        for M in sizes:
+            t0 = time.perf_counter(); r = b.mcc_derive(0, M, 1, seed=1); first = (time.perf_counter() - t0) * 1e3
+            ms = median_ms(lambda: b.mcc_derive(0, M, 1, seed=1), 20 if M <= 256 else 5)
+            inner = r.child0 >= 0
+            out["derive"].append({"M": M, "first_call_ms": first, "median_ms": ms, "distinct_clades": r.num_distinct_clades, "table_slots": r.table_slots, "table_regrows": r.table_regrows,
+                                  "master": r.master, "inner_nodes_with_support_below_1": int((r.support[inner] < 1).sum()), "least_support": float(r.support[inner].min())})
+            print("derive", M, ms, file=sys.stderr, flush=True)
+        if a.host_model:
+            import mcc_model as mm
+            ss = [mm.Sample(*b.tree_sample_get(i)) for i in range(min(32, sizes[-1]))]
+            t0 = time.perf_counter(); mm.derive_letter(ss, 1); out["host_model_a_M32_s"] = time.perf_counter() - t0
+    finally:
+        run.close(); b.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
