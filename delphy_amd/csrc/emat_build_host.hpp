@@ -1,5 +1,5 @@
 // emat_build_host.hpp -- host driver of emat_tree_build_usher_like (kernel and finishing passes in emat_build.hpp).
-// Included at the end of emat_backend.hip.
+// Included by emat_backend.hip after its entry points.
 #ifndef EMAT_BUILD_HOST_HPP_
 #define EMAT_BUILD_HOST_HPP_
 
@@ -47,7 +47,6 @@ std::string validate_tip_descs(const emat_tip_descs& td, const std::vector<uint8
 }
 
 emat_status build_usher_like(emat_backend* h, const emat_tip_descs& td, uint64_t seed) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const int n = td.num_tips, N = 2 * n - 1, L = h->L;
   const int nd_tot = td.delta_offset[n], nm_tot = td.miss_offset[n];
   int max_deltas = 0;
@@ -188,7 +187,7 @@ emat_status emat_tree_build_usher_like(emat_backend* h, const emat_tip_descs* ti
   h->built.valid = false;
   const std::string bad = validate_tip_descs(*tips, h->ref);
   if (!bad.empty()) return fail(h, EMAT_ERR_INVALID_ARGUMENT, "emat_tree_build_usher_like: " + bad);
-  if (h->host_only) return fail(h, EMAT_ERR_NO_DEVICE, "host-only handle (device = -1): the engine has no CPU fallback");
+  if (h->host_only) return no_device(h);
   // the builder's workgroups must all be resident: nothing of this handle may still be running (a pass, its side launches)
   { emat_status st = emat_synchronize(h); if (st) return st; }
   return build_usher_like(h, *tips, seed);

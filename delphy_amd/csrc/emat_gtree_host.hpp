@@ -3,7 +3,7 @@
 // around the few things that stay on the host: slab geometry, size classes, and the coalescent cell tables, which are
 // built from a skeleton (topology + times) of every part with the same code as on the host path.
 //
-// Included at the end of emat_backend.hip.
+// Included by emat_backend.hip after its entry points.
 #ifndef EMAT_GTREE_HOST_HPP_
 #define EMAT_GTREE_HOST_HPP_
 
@@ -25,7 +25,7 @@ emat_status gt_finish_gather(emat_backend* h);
 // `uploading`: emat_tree_upload, the one call that may follow a failed gather (it replaces the tree the gather left half written).
 emat_status gt_require(emat_backend* h, bool need_resident, bool gather_may_run = false, bool uploading = false) {
   if (!bind_device(h)) return fail(h, EMAT_ERR_HIP, "hipSetDevice failed");
-  if (h->host_only) return fail(h, EMAT_ERR_NO_DEVICE, "host-only handle (device = -1): the engine has no CPU fallback");
+  if (h->host_only) return no_device(h);
   if (uploading) return EMAT_OK;   // (whatever gather was pending or failed concerns the tree that is being replaced)
   if (need_resident && !h->gt.resident) return fail(h, EMAT_ERR_STATE, "emat_tree_upload first");
   // A deferred gather that failed (emat_tree_reassemble had already returned EMAT_OK with the new links) leaves the device-resident tree
@@ -38,7 +38,6 @@ emat_status gt_require(emat_backend* h, bool need_resident, bool gather_may_run 
 // After a reassemble: the packed children, the root and its time come over at once (1.6 MB at 200 000 nodes, into page-locked
 // memory); parent, children and times as separate arrays -- 4 MB more, which a cycle of the run driver never looks at -- on demand.
 emat_status gt_fetch_mirrors(emat_backend* h) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   const size_t n = (size_t)G.n;
   HIP_TRY(G.d_kids.alloc(n)); HIP_TRY(G.pin_kids.resize(n * sizeof(int2)));
@@ -53,7 +52,6 @@ emat_status gt_fetch_mirrors(emat_backend* h) {
 }
 // the walk records of k_gt_measure, when lists or links were written since they were last made (queued on the engine's stream)
 emat_status gt_ensure_climb(emat_backend* h) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   if (G.climb_current && G.climb.n >= (size_t)G.n) return EMAT_OK;
   HIP_TRY(G.climb.alloc((size_t)G.n));
@@ -63,7 +61,6 @@ emat_status gt_ensure_climb(emat_backend* h) {
   return EMAT_OK;
 }
 emat_status gt_full_mirrors(emat_backend* h) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   if (!G.full_mirrors_stale) return EMAT_OK;
   const size_t n = (size_t)G.n;
@@ -84,7 +81,6 @@ extern "C" {
 emat_status emat_tree_upload(emat_backend* h, const emat_flat_tree* tree) {
   if (!h || !tree) return EMAT_ERR_INVALID_ARGUMENT;
   emat_status st = gt_require(h, false, false, true); if (st) return st;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const std::string msg = validate_flat_tree(*tree, h->L);
   if (!msg.empty()) return fail(h, EMAT_ERR_INVALID_ARGUMENT, "emat_tree_upload: " + msg);
   { const std::string lim = flat_tree_list_limit(*tree, (int32_t)k_max_list_upload); if (!lim.empty()) return fail(h, EMAT_ERR_CAPACITY, "emat_tree_upload: " + lim); }
@@ -143,7 +139,6 @@ emat_status emat_tree_get_sizes(emat_backend* h, int32_t* nn, int32_t* nm, int32
 emat_status emat_tree_download(emat_backend* h, emat_flat_tree* out, uint8_t* ref_sequence) {
   if (!h || !out) return EMAT_ERR_INVALID_ARGUMENT;
   emat_status st = gt_require(h, true); if (st) return st;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   if (G.parts_live) return fail(h, EMAT_ERR_STATE, "the parts are out on their slabs: emat_tree_reassemble first");
   st = gt_full_mirrors(h); if (st) return st;
@@ -207,7 +202,6 @@ emat_status emat_tree_get_kids(emat_backend* h, const int32_t** kids, int32_t* n
 emat_status emat_tree_partition(emat_backend* h, int32_t num_cuts, const int32_t* cut_nodes, int32_t* num_parts, int32_t* root_part, int32_t* part_sizes) {
   if (!h || num_cuts < 0 || (num_cuts > 0 && !cut_nodes) || !num_parts || !root_part) return EMAT_ERR_INVALID_ARGUMENT;
   emat_status st = gt_require(h, true); if (st) return st;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   if (G.parts_live) return fail(h, EMAT_ERR_STATE, "the parts are out on their slabs: emat_tree_reassemble first");
   const int n = G.n;
@@ -297,7 +291,6 @@ emat_status emat_tree_partition(emat_backend* h, int32_t num_cuts, const int32_t
 }
 
 namespace { emat_status gt_partition_to_host(emat_backend* h) {   // the arrays of a partition made on the device, when the host wants them after all
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   if (!G.h_orig.empty() || G.P == 0) return EMAT_OK;
   const size_t total = (size_t)G.h_part_off[G.P];
@@ -332,7 +325,6 @@ emat_status emat_tree_repartition_range(emat_backend* h, int32_t num_parts, cons
   if (!h || num_parts <= 0 || (!made_here && (!part_offset || !orig || !kid0 || !kid1)) || !seeds || !pm || !(t_step > 0.0) || root_part < 0 || root_part >= num_parts) return EMAT_ERR_INVALID_ARGUMENT;
   if (part_lo < 0 || part_hi > num_parts || part_lo >= part_hi) return EMAT_ERR_INVALID_ARGUMENT;
   emat_status st = gt_require(h, true); if (st) return st;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   if (h->cfg.max_parts > 0 && num_parts > h->cfg.max_parts) return fail(h, EMAT_ERR_INVALID_ARGUMENT, "more parts than cfg.max_parts");
   if (!h->have_ref || !h->have_evo) return fail(h, EMAT_ERR_STATE, "set_ref_sequence and set_evo must precede emat_tree_repartition");
   GTreeHost& G = h->gt;
@@ -418,7 +410,6 @@ emat_status emat_tree_repartition_range(emat_backend* h, int32_t num_parts, cons
     return EMAT_OK;
   };
   st = join_side_classes(h); if (st) return st;   // (side launches of a pass nobody gathered: the slabs are about to be rebuilt)
-  h->sides_must_fork = true;
   if (!measure_queued) { st = launch_measure(); if (st) return st; }
   laps.mark("tree_repartition: 02 join sides + launch k_gt_measure");
   // The records of the parts.  With the coalescent tables built on the host they come first (the builder reads the parts' skeletons:
@@ -431,7 +422,7 @@ emat_status emat_tree_repartition_range(emat_backend* h, int32_t num_parts, cons
   h->parts.resize(nloc);
   h->expected_moves.assign((size_t)nloc, 0);
   h->uploads_expected = 0; h->root_part = (root_part >= lo && root_part < hi) ? root_part - lo : -1;
-  h->slabs_on_device = false; h->host_slabs_current = false; h->headers_current = false; h->have_coal = false; h->derived_valid = false;
+  h->parts_replaced();
   auto init_record = [&](int q) {
     const int p = lo + q;
     PartHost& ph = h->parts[q];
@@ -612,7 +603,7 @@ emat_status emat_tree_repartition_range(emat_backend* h, int32_t num_parts, cons
     HIP_TRY(hipStreamSynchronize(h->stream));
     laps.mark("tree_repartition: 13 wait for the kernels");
     HIP_TRY(hipMemcpy(&cst, G.status.p, sizeof(cst), hipMemcpyDeviceToHost));
-    if (cst != k_gt_ok) { h->slabs_on_device = false; h->parts.clear(); return fail(h, EMAT_ERR_INVALID_ARGUMENT, "coalescent grid: a lineage outside its part's cells, or an inactive final cell"); }
+    if (cst != k_gt_ok) { h->device_build_failed(); h->parts.clear(); return fail(h, EMAT_ERR_INVALID_ARGUMENT, "coalescent grid: a lineage outside its part's cells, or an inactive final cell"); }
     // the run-wide cell arrays ARE the grid the kernels just built: the moves read them in place; the host's mirror of them (a few KB,
     // read when slabs are decoded) follows when a pull asks for it (pull_grid_mirrors)
     h->shared_dev = SharedCells{G.co_k_tw.p, G.co_tsop.p, G.co_num_active.p, co.num_cells};
@@ -620,7 +611,7 @@ emat_status emat_tree_repartition_range(emat_backend* h, int32_t num_parts, cons
     h->sh_ktw.clear(); h->sh_popsize.clear(); h->sh_tsop.clear(); h->sh_nact.clear();
   } else { emat_status st2 = upload_shared_cells(h); if (st2) return st2; h->grid_mirrors_on_device = false; }
   laps.mark("tree_repartition: 14 status of the grid");
-  h->slabs_on_device = true; h->host_slabs_current = false; h->headers_current = false; h->derived_valid = false;
+  h->device_built_slabs();
   G.parts_live = true;
   if (verbose) {
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -637,7 +628,6 @@ namespace {
 
 // the heaps must keep what they hold (the nodes gathered so far) when they grow
 template <class T> emat_status gt_grow_keeping(emat_backend* h, DevBuf<T>& buf, size_t used, size_t want) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   if (want <= buf.n) return EMAT_OK;
   DevBuf<T> bigger;
   HIP_TRY(bigger.alloc(want));
@@ -647,7 +637,6 @@ template <class T> emat_status gt_grow_keeping(emat_backend* h, DevBuf<T>& buf, 
 }
 
 emat_status gt_root_deltas(emat_backend* h, std::vector<GRootDelta>& rd, bool& owner) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   owner = G.root_part >= G.lo && G.root_part < G.hi;
   rd.clear();
@@ -671,7 +660,6 @@ emat_status gt_root_deltas(emat_backend* h, std::vector<GRootDelta>& rd, bool& o
 // every local part writes the nodes it owns into this process's copy of the tree; the heaps are rebuilt from zero
 // (in two halves: the launch, and the wait + check, which a single process postpones until somebody needs the tree: gt_finish_gather)
 emat_status gt_launch_gather(emat_backend* h) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   G.climb_current = false;   // (lists and links are about to be rewritten)
   HIP_TRY(hipMemsetAsync(G.tops.p, 0, 3 * sizeof(uint32_t), h->stream));
@@ -693,7 +681,6 @@ emat_status gt_finish_gather(emat_backend* h) {
   return st;
 }
 emat_status gt_finish_gather_once(emat_backend* h) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   int32_t status = 0;
   for (int attempt = 0;; ++attempt) {
@@ -716,7 +703,6 @@ emat_status gt_finish_gather_once(emat_backend* h) {
   return EMAT_OK;
 }
 emat_status gt_gather_local(emat_backend* h, const std::vector<GRootDelta>& rd, bool wait = true) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   const size_t room = std::max<size_t>(rd.size(), (size_t)k_gt_max_root_deltas);
   HIP_TRY(G.root_deltas.alloc(room)); HIP_TRY(G.n_root_deltas.alloc(1)); HIP_TRY(G.root_deltas_in.alloc(room));
@@ -759,7 +745,6 @@ emat_status emat_tree_reassemble(emat_backend* h, int32_t* num_root_deltas, int3
   // One process holds every part.  What the host needs to draw the next partition -- the links, the root, the changes of the root
   // sequence -- is written and fetched first (three small kernels, one wait); the gather of every list follows and is NOT waited
   // for: it runs while the caller picks and refines its next stencil, and whoever touches the tree next finishes it (gt_require).
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   std::vector<GRootDelta> rd;
   {
     const size_t n = (size_t)G.n;
@@ -820,7 +805,6 @@ emat_status emat_tree_gather_local(emat_backend* h, int32_t num_root_deltas, con
 emat_status emat_tree_export_nodes(emat_backend* h, uint8_t* buf, uint64_t capacity, uint64_t* bytes_needed) {
   if (!h || !bytes_needed) return EMAT_ERR_INVALID_ARGUMENT;
   emat_status st = gt_require(h, true); if (st) return st;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   if (!G.parts_live) return fail(h, EMAT_ERR_STATE, "emat_tree_repartition and emat_tree_gather_local first");
   // one entry per node of every local part (k_gt_export's comment says what an entry carries)
@@ -865,7 +849,6 @@ emat_status emat_tree_export_nodes(emat_backend* h, uint8_t* buf, uint64_t capac
 emat_status emat_tree_apply_nodes(emat_backend* h, const uint8_t* buf, uint64_t bytes) {
   if (!h || !buf || bytes < 32) return EMAT_ERR_INVALID_ARGUMENT;
   emat_status st = gt_require(h, true); if (st) return st;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   if (!G.parts_live) return fail(h, EMAT_ERR_STATE, "emat_tree_repartition and emat_tree_gather_local first");
   // `buf` may be host or device memory (what an all-gather on device buffers delivers): the header and the entries are checked on

@@ -2,7 +2,7 @@
 // state checks, sizes, the launches, and the two things that stay on the host because they are a few thousand flops: turning
 // the per-sample histograms into log clade credibilities and picking the master (mcc_tree.cpp:78-108).
 //
-// Included at the end of emat_backend.hip, after emat_gtree_host.hpp (gt_require).
+// Included by emat_backend.hip after its entry points, after emat_gtree_host.hpp (gt_require).
 #ifndef EMAT_MCC_HOST_HPP_
 #define EMAT_MCC_HOST_HPP_
 
@@ -15,7 +15,6 @@ std::string mcc_mb(size_t bytes) { return std::to_string((bytes + (1u << 20) - 1
 
 // EMAT_ERR_CAPACITY, with the sizes, when the device does not have `bytes` free (an allocation that fails later would be EMAT_ERR_HIP).
 emat_status mcc_check_room(emat_backend* h, const std::string& w, size_t bytes, const std::string& what_for) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   if (bytes > free_b) return fail(h, EMAT_ERR_CAPACITY, w + ": " + what_for + " needs " + mcc_mb(bytes) + ", the device has " + mcc_mb(free_b) + " free of " + mcc_mb(total_b));
@@ -24,7 +23,6 @@ emat_status mcc_check_room(emat_backend* h, const std::string& w, size_t bytes, 
 
 // (Re)binds the store to `capacity` samples of `n` nodes.  Frees what it held first, so that the room it asks for is the room it needs.
 emat_status mcc_store_alloc(emat_backend* h, const std::string& w, int64_t capacity, int32_t n) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   MccHost& X = h->mcc;
   const size_t nodes = (size_t)capacity * (size_t)n;
   const size_t store_bytes = nodes * k_mcc_store_bytes_per_node + (size_t)capacity * 4, derive_bytes = nodes * k_mcc_derive_bytes_per_node + (size_t)n * 64;
@@ -103,7 +101,6 @@ emat_status emat_tree_samples_reserve(emat_backend* h, int32_t capacity) {
 /* Base_tree_vector::push_back of a copy of the run's tree, delphy_ui.cpp:770-773 (header: emat_tree_sample_push) */
 emat_status emat_tree_sample_push(emat_backend* h, int32_t* index) {
   if (!h) return EMAT_ERR_INVALID_ARGUMENT;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const std::string w = "emat_tree_sample_push";
   emat_status st = mcc_require(h, w, true); if (st) return st;
   st = mcc_require_store(h, w); if (st) return st;
@@ -124,7 +121,6 @@ emat_status emat_tree_sample_push(emat_backend* h, int32_t* index) {
 /* (header: emat_tree_sample_push_flat) */
 emat_status emat_tree_sample_push_flat(emat_backend* h, int32_t num_nodes, const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* t, int32_t root, int32_t* index) {
   if (!h) return EMAT_ERR_INVALID_ARGUMENT;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const std::string w = "emat_tree_sample_push_flat";
   emat_status st = mcc_require(h, w, false); if (st) return st;
   st = mcc_require_store(h, w); if (st) return st;
@@ -166,7 +162,6 @@ emat_status emat_tree_samples_clear(emat_backend* h) {
 /* (header: emat_tree_sample_get) */
 emat_status emat_tree_sample_get(emat_backend* h, int32_t index, int32_t* parent, int32_t* child0, int32_t* child1, double* t, int32_t* root) {
   if (!h) return EMAT_ERR_INVALID_ARGUMENT;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const std::string w = "emat_tree_sample_get";
   emat_status st = gt_require(h, false, true); if (st) return st;
   MccHost& X = h->mcc;
@@ -184,7 +179,6 @@ emat_status emat_tree_sample_get(emat_backend* h, int32_t index, int32_t* parent
 /* derive_mcc_tree (mcc_tree.cpp:58-156) + Mcc_tree::calculate_derived_quantities (:158-179) (header: emat_mcc_derive) */
 emat_status emat_mcc_derive(emat_backend* h, int32_t first, int32_t count, int32_t stride, uint64_t seed, emat_mcc_result* out) {
   if (!h || !out) return EMAT_ERR_INVALID_ARGUMENT;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const std::string w = "emat_mcc_derive";
   emat_status st = gt_require(h, false, true); if (st) return st;
   MccHost& X = h->mcc;
@@ -283,7 +277,6 @@ emat_status emat_mcc_derive(emat_backend* h, int32_t first, int32_t count, int32
 /* corresponding_node_to (mcc_tree.h:91-98) for every MCC node (header: emat_mcc_get_correspondence) */
 emat_status emat_mcc_get_correspondence(emat_backend* h, int32_t k, int32_t* node_in_sample, uint8_t* is_exact) {
   if (!h) return EMAT_ERR_INVALID_ARGUMENT;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const std::string w = "emat_mcc_get_correspondence";
   emat_status st = gt_require(h, false, true); if (st) return st;
   MccHost& X = h->mcc;

@@ -1,7 +1,7 @@
 // emat_probe_host.hpp -- host side of the tree probers (emat_probe_kernels.hpp): argument checks as the reference's constructors
 // and probers make them, the grid (with the reference's crude extension towards a root that lies before t_start), the launches.
 //
-// Included at the end of emat_backend.hip, after emat_gtree_host.hpp (gt_require).
+// Included by emat_backend.hip after its entry points, after emat_gtree_host.hpp (gt_require).
 #ifndef EMAT_PROBE_HOST_HPP_
 #define EMAT_PROBE_HOST_HPP_
 
@@ -63,7 +63,6 @@ emat_status probe_make_plan(emat_backend* h, const char* what, const ProbeReques
 
 // Steps 1 and 2: the branch counts of `plan`, left in h->probe.counts on the engine's stream.
 emat_status probe_branch_counts(emat_backend* h, const ProbeRequest& q, const ProbePlan& plan) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   GTreeHost& G = h->gt;
   const int n = G.n;
   const ProbeGrid& g = plan.grid;
@@ -106,7 +105,6 @@ emat_status probe_branch_counts(emat_backend* h, const ProbeRequest& q, const Pr
 }
 
 emat_status probe_check_status(emat_backend* h, const char* what) {
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   int32_t s = 0;
   HIP_TRY(hipMemcpy(&s, h->probe.status.p, sizeof(int32_t), hipMemcpyDeviceToHost));
   if (s == k_probe_negative_branch) return fail(h, EMAT_ERR_INTERNAL, std::string(what) + ": a node of the resident tree is earlier than its parent (the reference's add_boxcar refuses left > right)");
@@ -116,7 +114,6 @@ emat_status probe_check_status(emat_backend* h, const char* what) {
 // Tree_prober (step 3) on the counts probe_branch_counts left behind; p [num_members * num_t_cells], member-major.
 emat_status probe_run(emat_backend* h, const char* what, const emat_pop_model* pm, const ProbeRequest& q, double* p) {
   if (!h || !pm || !p) return EMAT_ERR_INVALID_ARGUMENT;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const std::string w(what);
   if (pm->kind == EMAT_POP_SKYGRID && pm->skygrid_num_knots > 0 && (!pm->skygrid_x || !pm->skygrid_gamma)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": a Skygrid model without its knots");
   HostPopModel hp;
@@ -172,7 +169,6 @@ emat_status emat_tree_probe_site_states(emat_backend* h, const emat_pop_model* p
 emat_status emat_tree_branch_counts(emat_backend* h, int32_t kind, int32_t num_marked, const int32_t* marked_nodes, int32_t site, double t_start, double t_end, int32_t num_t_cells,
                                     int32_t* num_cells, int32_t* cells_to_skip, double* x_start, double* counts, int64_t counts_capacity) {
   if (!h || !num_cells) return EMAT_ERR_INVALID_ARGUMENT;
-  auto set_error = [&](const std::string& s) { h->set_error(s); };
   const ProbeRequest q{kind, num_marked, marked_nodes, site, t_start, t_end, num_t_cells};
   ProbePlan plan{};
   emat_status st = probe_make_plan(h, "emat_tree_branch_counts", q, plan); if (st) return st;

@@ -21,6 +21,10 @@ namespace emat {
 
 constexpr uint32_t k_slab_magic = 0x454D4154u;  // "EMAT"
 
+// SlabHeader::fail_line of a part whose ticket found that its predecessor had run on another XCD (run_moves_body): like the -3 of the
+// misplaced LDS block it is no source line, and finish_pass tells the two apart by value.
+constexpr int32_t k_fail_line_other_xcd = -227;
+
 enum PartStatus : int32_t {
   k_part_ok = 0,
   k_part_need_space = 101,     // stopped BEFORE a move: heap reserve or scratch too small (state is consistent)

@@ -4,7 +4,7 @@
 // best-first search from wherever the previous tip went in (branch and bound on the Fitch cost), the tree is rebuilt in nearest-first
 // order until that stops helping, refined by subtree-prune-and-regraft moves, rooted by the regression of divergence on sampling date,
 // and dated from the fitted rate -- and runs once per run in seconds where the UShER-like builder (emat_build.hpp) is quadratic.
-// Included at the end of emat_backend.hip (after emat_build_host.hpp, whose closing passes and checks it shares).
+// Included by emat_backend.hip after its entry points (after emat_build_host.hpp, whose closing passes and checks it shares).
 //
 // Layout.  The unrooted tree is struct-of-arrays: arcs come in mate pairs (a ^ 1), arc a holds its target and the site deltas
 // origin -> target as a site-sorted vector (the reference: a hash map per arc); a node holds up to three arc slots and the arc that

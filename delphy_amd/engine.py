@@ -33,14 +33,12 @@ def library_path() -> str:
     return os.environ.get("EMAT_LIB_PATH") or os.path.join(_HERE, _LIB_NAME)
 
 
-_DEVSRC = ("emat_backend.hip", "emat_device_core.hpp", "emat_device_moves.hpp", "emat_device_spr.hpp", "emat_slab.hpp", "emat_gtree_kernels.hpp", "emat_build.hpp", "emat_probe_kernels.hpp", "emat_mcc_kernels.hpp", "Makefile")
-
-
 def source_build_id() -> str:
-    """The id csrc/Makefile would stamp into a library built from the sources as they are now (same files, same order)."""
+    """The id csrc/Makefile would stamp into a library built from the sources as they are now: the files of its DEVSRC line, in its order."""
     import hashlib
+    devsrc = [line for line in open(os.path.join(_CSRC, "Makefile")) if line.startswith("DEVSRC =")][0]
     h = hashlib.sha256()
-    for f in _DEVSRC:
+    for f in devsrc.split("=", 1)[1].split("#")[0].split():
         h.update(open(os.path.join(_CSRC, f), "rb").read())
     return h.hexdigest()[:16]
 

@@ -41,9 +41,8 @@ def build():
         p = tmp + "/delphy_amd/csrc/" + f
         t, n = instrument(open(p).read(), fid); open(p, "w").write(t); print(f, n, "functions instrumented")
     out = ROOT + "/delphy_amd/libemat_calls.so"
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-function", "-Wno-unused-result", "-mllvm", "-amdgpu-lower-module-lds-strategy=module", "-DEMAT_COUNT_CALLS",
-           '-DEMAT_BUILD_ID="calls"', "-shared", "-o", out, "emat_backend.hip", "emat_run.cpp", "emat_dphy.cpp", "emat_multi.cpp", "-ldl"]
-    subprocess.run(cmd, cwd=tmp + "/delphy_amd/csrc", check=True, stderr=subprocess.DEVNULL)
+    # sources and flags are the copied csrc/Makefile's; the id names the instrumented build
+    subprocess.run(["make", "-B", "-C", tmp + "/delphy_amd/csrc", "OUT=" + out, "EXTRA_FLAGS=-DEMAT_COUNT_CALLS", "BUILD_ID=calls"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     print("built", out)
 
 

@@ -242,7 +242,7 @@ def test_a_re_materialisation_in_mid_pass_keeps_what_the_moves_maintain():
     sweep): the root part outgrows its coalescent grid in the second pass (401 -> 2 027 cells), every part is re-encoded, and in another
     part a node under which every site is missing below one child or the other -- d log G / dt = lambda - lambda exactly -- took the uniform
     branch of the bounded exponential in the reference's arithmetic and the other branch with a recomputed lambda_i two units in the last
-    place off: one move skipped its acceptance draw and the chains parted.  Now the maintained values are carried over (PartHost, emat_backend.hip):
+    place off: one move skipped its acceptance draw and the chains parted.  Now the maintained values are carried over (PartHost, emat_state_host.hpp):
     two passes, every part's trace equal move for move, lambda_i equal BIT for bit."""
     from helpers import random_scenario
     rng = np.random.default_rng(6202)
