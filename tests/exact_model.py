@@ -14,7 +14,14 @@ roundings inside each term).  Rules for the terms:
 - a factor exp(x) counts its result times (1 + |x|) (a relative error e of x is a relative error |x| e of exp(x)), and a
   log(y) counts |log y| + 1 plus the magnitude of whatever exponent y carries;
 - a quantity built on another one (lambda inside a branch's log G, k_bar inside a cell's prior term) counts that one's S
-  times the factor it is multiplied by, and adds its n.
+  times the factor it is multiplied by, and adds its n;
+- a difference of two states (`partial_log_prior_delta`, `part_log_G_delta`: what one accepted move changed) counts only the
+  terms that differ between them, each with the S its own rule above gives it in the state before plus in the state after:
+  whatever both states hold alike is never formed by a code that computes the difference, so the bound does not carry the
+  total's magnitude.  A cell of the grid differs when its exact k_bar_p differs, an inner node's -log N(t) when its time
+  does, a branch when its parent, end times, mutations or lambda do, the root prior when the root's state counts do;
+- a term that a move adds to a log MH ratio and takes away again (a displacement's delta log G = d_logG_dt (new_t - old_t)
+  and its proposal ratio, the same product) counts twice its magnitude: the sum rounds while it holds that term.
 
 Reference lines of the definitions: core/pop_model.cpp:18-145, 181-204, 247-330; core/phylo_tree_calc.cpp:67-93,
 120-371, 390-436, 458-635 and phylo_tree_calc.h:185-210; core/subrun.cpp:17-56; core/scalable_coalescent.cpp:23-187;
@@ -50,6 +57,9 @@ class Exact:
         return (self.n + 8) * U * float(self.S)
 
     def err(self, x) -> float:
+        """`x`: a float64, or a Fraction (the exact difference of two float64 values an engine reported)."""
+        if isinstance(x, F):
+            return float(abs(x - self.value)) if isinstance(self.value, F) else math.inf
         x = float(x)
         if not isinstance(self.value, F):
             return 0.0 if x == self.value else math.inf
@@ -381,6 +391,15 @@ class Derived:
         if brute:
             self.lam = self._brute_lambda()
 
+    def retimed(self, tree):
+        """The Derived of a tree that differs from this one's in node and mutation TIMES only: lambda_i and the missing-site
+        counts depend on none of them."""
+        d = object.__new__(Derived)
+        for k, v in self.__dict__.items():
+            setattr(d, k, v)
+        d.T = _Tree(tree)
+        return d
+
     def _brute_lambda(self):
         """lambda at every node straight from the definition: the node's whole sequence, site by site."""
         T, ref, evo = self.T, self.ref, self.evo
@@ -590,8 +609,9 @@ def _grid(intervals, cell_of, lb_of, ub_of, c0, c1, t_step, bound_mag):
                 continue
             part[i] += (chi - clo) / t_step
             S[i] += (chi - clo) / t_step
-        if cb - ca >= 2:
-            full[ca + 1 - c0] += 1; full[cb - c0] -= 1
+        flo, fhi = max(ca + 1, c0), min(cb, c1 + 1)      # the cells it crosses whole, within c0..c1
+        if flo < fhi:
+            full[flo - c0] += 1; full[fhi - c0] -= 1
     run = 0
     kb = []
     for i in range(ncell):
@@ -660,6 +680,123 @@ def partial_log_prior(tree, pop: Pop, includes_tree_root, tables) -> Exact:
             a, b = pop.neg_log_pop(T.t[X])
             v += a; S += b; ninner += 1
     return Exact(v, S, 4 * n + ninner + nmax)
+
+
+class ExactDelta(Exact):
+    """An Exact difference between two states.  `cells` = {cell: (k_bar_p before, after)} of the grid cells that differ and
+    `k_sensitivity` = the sum over them of |d term / d k_bar_p| = |w (k A - c)| at the larger of the two (what an error of the
+    engine's MAINTAINED k_bar_p, on which it evaluates the prior, is multiplied by); `branches` = the branches that differ."""
+    __slots__ = ("cells", "k_sensitivity", "branches", "root_prior_differs")
+
+    def __init__(self, value, S, n):
+        Exact.__init__(self, value, S, n)
+        self.cells, self.k_sensitivity, self.branches, self.root_prior_differs = {}, _ZERO, [], False
+
+
+def _part_intervals(T: _Tree, includes_tree_root, tr, ts, num_cells):
+    iv = _lineage_intervals(T)
+    if includes_tree_root:
+        iv.append((tr - num_cells * ts, T.t[T.root]))
+    return iv
+
+
+def partial_log_prior_delta(before, after, pop: Pop, includes_tree_root, tables) -> ExactDelta:
+    """partial_log_prior(after) - partial_log_prior(before), both on `tables` (those read AFTER the move: cells the root part's
+    grid appended during it hold the same lineage above the root in both trees, or differ and are counted), over the cells
+    whose exact k_bar_p differs and the inner nodes whose time differs.  Per cell and node the S of partial_log_prior's rule,
+    before plus after."""
+    from collections import Counter
+    B = before if isinstance(before, _Tree) else _Tree(before)
+    A = after if isinstance(after, _Tree) else _Tree(after)
+    assert A.n == B.n
+    n = len(tables["k_bar_p"])
+    tr, ts = _fl(tables["t_ref"]), _fl(tables["t_step"])
+    ivB, ivA = _part_intervals(B, includes_tree_root, tr, ts, n), _part_intervals(A, includes_tree_root, tr, ts, n)
+    cB, cA = Counter(ivB), Counter(ivA)
+    changed = list((cB - cA).keys()) + list((cA - cB).keys())
+    out = ExactDelta(_ZERO, _ZERO, 0)
+    v, S, nterms, nmax = _ZERO, _ZERO, 0, 0
+    if changed:
+        cell_of = lambda t: _floor((tr - t) / ts)
+        lb_of, ub_of = (lambda c: tr - (c + 1) * ts), (lambda c: tr - c * ts)
+        ends = [cell_of(t) for iv in changed for t in iv]
+        c0, c1 = max(0, min(ends)), min(n - 1, max(ends))
+        tlo, thi = lb_of(c1), ub_of(c0)
+        mag = lambda c: abs(tr) + abs((c + 1) * ts)
+        near = lambda ivs: [(lo, hi) for lo, hi in ivs if hi >= tlo and lo <= thi]
+        kB, SB, nB = _grid(near(ivB), cell_of, lb_of, ub_of, c0, c1, ts, mag)
+        kA, SA, nA = _grid(near(ivA), cell_of, lb_of, ub_of, c0, c1, ts, mag)
+        for j, i in enumerate(range(c0, c1 + 1)):
+            if kB[j] == kA[j]:
+                continue
+            out.cells[i] = (kB[j], kA[j])
+            Ap = int(tables["num_active_parts"][i])
+            assert Ap > 0, "cell %d: the part has lineages there but the table says %d active parts" % (i, Ap)
+            pb, ktp, kt = _fl(tables["popsize_bar"][i]), _fl(tables["k_twiddle_bar_p"][i]), _fl(tables["k_twiddle_bar"][i])
+            c = ktp * Ap - kt + F(1, 2)
+            w = ts / pb
+            sens = _ZERO
+            for sign, k, kS in ((-1, kB[j], SB[j]), (1, kA[j], SA[j])):
+                v -= sign * w * (F(1, 2) * k * k * Ap - c * k)
+                s1 = abs(w * (k * Ap - c))
+                S += w * (F(1, 2) * k * k * Ap + (abs(ktp * Ap) + abs(kt) + F(1, 2)) * abs(k)) + s1 * kS
+                sens = max(sens, s1)
+            out.k_sensitivity += sens
+            nterms += 8
+            nmax = max(nmax, nB[j], nA[j])
+    for X in range(A.n):
+        if A.kids[X] and A.t[X] != B.t[X]:
+            a, sa = pop.neg_log_pop(A.t[X])
+            b, sb = pop.neg_log_pop(B.t[X])
+            v += a - b; S += sa + sb; nterms += 2
+    out.value, out.S, out.n = v, S, nterms + nmax
+    return out
+
+
+def part_log_G_delta(before, after, ref, evo: Evo, includes_run_root) -> ExactDelta:
+    """part_log_G(after) - part_log_G(before) over the branches whose parent, end times, mutations or lambda differ, and the
+    root prior when the root's state counts do.  `before` / `after`: trees, or the `Derived` of them."""
+    DB = before if isinstance(before, Derived) else Derived(before, ref, evo)
+    DA = after if isinstance(after, Derived) else Derived(after, ref, evo)
+    B, A = DB.T, DA.T
+    assert A.n == B.n
+    out = ExactDelta(_ZERO, _ZERO, 0)
+    v, S, n, nl = _ZERO, _ZERO, 0, 0
+    for X in range(A.n):
+        inB, inA = X != B.root, X != A.root
+        if inB and inA and B.parent[X] == A.parent[X] and B.t[X] == A.t[X] and B.t[B.parent[X]] == A.t[A.parent[X]] \
+                and DB.lam[X] == DA.lam[X] and B.muts[X] == A.muts[X]:
+            continue
+        if not inB and not inA:
+            continue
+        out.branches.append(X)
+        if inA:
+            a, b, c = DA.branch_log_G(X); v += a; S += b; n += c; nl = max(nl, DA.lam_n[X])
+        if inB:
+            a, b, c = DB.branch_log_G(X); v -= a; S += b; n += c; nl = max(nl, DB.lam_n[X])
+    if includes_run_root and (DB.root_state_counts() != DA.root_state_counts()):
+        rB, rA = DB.log_root_prior(), DA.log_root_prior()
+        assert isinstance(rB.value, F) and isinstance(rA.value, F), "a root state of prior probability 0"
+        v += rA.value - rB.value; S += rA.S + rB.S; n += rA.n + rB.n
+        out.root_prior_differs = True
+    out.value, out.S, out.n = v, S, n + nl
+    return out
+
+
+def displacement_slope(dv: "Derived", node) -> F:
+    """d log G / d t of one node's time inside the window its neighbouring mutations leave it, from the definitions: the branch
+    above it lengthens at -lambda(node); each child's branch shortens at the rate just below the node, which is the node's
+    rate less what the child's missing intervals take away (every newly missing site at the state it had at the node)."""
+    T, evo, ref, cum = dv.T, dv.evo, dv.ref, dv.cum
+    d = _ZERO if node == T.root else -dv.lam[node]
+    for c in T.kids[node]:
+        below = dv.lam[node]
+        for s, e in T.miss[c]:
+            below -= cum[e] - cum[s]
+        for l, st in T.mfs[c].items():
+            below -= evo.rate(l, st) - evo.rate(l, ref[l])
+        d += below
+    return d
 
 
 def scalable_log_prior(tree, pop: Pop, t_ref, t_step) -> Exact:

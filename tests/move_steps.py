@@ -1,0 +1,453 @@
+"""One move at a time: the engine's DECISIONS against the exact posterior of tests/exact_model.py.
+
+`step_chain` advances every part's chain by one move per pass on an OracleEngine or an EmatBackend and hands `on_step` the
+part's state before and after each move; `check_step` holds the move's trace row and the increments of the maintained totals
+to the identities the move code implies (emat_device_moves.hpp; the reference's core/subrun.cpp:148-320, 683-742):
+
+- a tip displacement, or the displacement of an inner node other than the run's root, proposes the new time from a bounded
+  exponential with exactly the slope of log G, so delta log G and the proposal ratio are the same product and
+  log_mh = partial prior(after) - partial prior(before); and log G is linear in that time: log G(after) - log G(before) =
+  d_logG_dt (new_t - old_t) EXACTLY, with d_logG_dt rebuilt from exact lambda_i and the exact rate change across the children's
+  missing intervals (exact_model.displacement_slope), as Fractions;
+- the displacement of the run's root is a symmetric step: log_mh = delta log G + delta partial prior;
+- a branch reform re-times one branch's mutations uniformly: log_mh = delta log G, the prior and k_bar_p untouched;
+- for all five kinds the increment of the maintained log_G and log_aug_prior over the one move is the exact difference.
+
+Bounds.  A log_mh or an increment is held to the `Exact.bound()` of the difference, whose S holds only the terms that differ
+(exact_model's docstring).  Added to it, each named:
+- the engine evaluates the prior on its MAINTAINED k_bar_p, so a prior difference (log_mh and the log_aug_prior increment, the
+  same number) gets the sum over the cells that differ of |w (k A - c)| times check_part's k_bar_p allowance at that move count;
+- the increment of a total gets 2 u max(|total before|, |total after|): the one addition at the total's magnitude;
+- a simple displacement's log_mh adds delta log G and takes the proposal ratio, the same product, away again: twice that
+  product's magnitude joins S (exact_model's docstring, last rule).
+
+One row, two decisions.  In the part that holds the run's root, a branch reform of a child of the root first runs
+spr_move_core in place (subrun.cpp:298-303: the mutations of both root branches "dance"), which accepts or rejects on its own
+and leaves no trace row; the row holds the reform's log_mh alone.  Between the two no state can be read, so for these steps
+(`compound`) log_mh has no identity over the states before and after; the increments of both totals, which cover both
+decisions together, and the validity of the new state are checked, and the steps are counted apart.
+
+A move that is not accepted (rejected, or an early return with a NaN log_mh) leaves log_G, log_aug_prior, k_bar_p (cells the
+root part's grid appended while it evaluated the proposal aside: they hold 1), the topology (after a rejected topology move a
+node's two children may have changed slots: the pruned subtree goes back under its old parent as its other child), every node
+time and every mutation's site and states bit for bit as they were.  Mutation times and lambda_i after a rejected TOPOLOGY move,
+as established on the CPU oracle over every rejected subtree slide and SPR1 move of test_move_steps.py's cases:
+- mutation times come back bit for bit (peel_graft followed by apply_graft of the old graft puts back the very doubles it took
+  out), and so they are asserted of the device -- but for a subtree pruned from under the RUN'S ROOT: the rooty graft reflects
+  the sibling branch's mutations about the root's time and back (t -> t_P - (t - t_P) -> t_P + (t_P - t'), four roundings),
+  and those times are held to 4 u (|t_P| + |t - t_P|), all others bit for bit;
+- lambda_i is NOT always bit-identical: hopping the pruned subtree up and down the tree recomputes the lambda of the nodes it
+  passes, and the rooty graft recomputes the root's from its child's.  Where it differs it is held to its Exact bound; where
+  it does not (most rejected moves, and every simple move) the bits are asserted.
+"""
+from fractions import Fraction as F
+
+import numpy as np
+
+import exact_model as X
+
+KINDS = ("inner_node_displace", "tip_displace", "branch_reform", "subtree_slide", "spr1")
+_TOPO = ("root", "parent", "child0", "child1", "t_min", "t_max", "mut_offset", "miss_offset", "miss_start", "miss_end", "mfs_offset", "mfs_site", "mfs_state")
+_MUT = ("mut_site", "mut_from", "mut_to")
+
+
+# ---- the stepper ----------------------------------------------------------------------------------------------------
+def snapshot(engine, p):
+    """What one part holds now.  (A device engine is synchronised by step_chain before this reads it.)"""
+    st = engine.part_stats(p)
+    tree = engine.part_download(p)
+    lam, nsm, G, A = engine.part_derived(p, tree.num_nodes)
+    tr = engine.part_trace(p, max(int(st["moves_done"]), 1))
+    return dict(tree=tree, lam=lam, nsm=nsm, G=float(G), A=float(A), tab=engine.part_coalescent(p), stats=st,
+                row=tr[-1].copy() if tr.shape[0] else None, trace_len=tr.shape[0])
+
+
+def advance_one_move(engine):
+    if hasattr(engine, "synchronize"):
+        engine.run_moves_per_part(1); engine.synchronize()
+    else:
+        engine.run_moves_per_part(1, threads=1)
+
+
+def step_chain(engine, part_ids, steps, on_step, advance=advance_one_move):
+    """`steps` passes of one move per part; on_step(p, step, before, after) for every watched part after every pass."""
+    if hasattr(engine, "synchronize"):
+        engine.synchronize()
+    import time
+    prev = {p: snapshot(engine, p) for p in part_ids}
+    cost = step_chain.cost = dict(passes=0, advance_s=0.0, read_s=0.0)      # what the engine's side of a pass takes
+    for s in range(steps):
+        t0 = time.perf_counter()
+        advance(engine)
+        t1 = time.perf_counter()
+        curs = {p: snapshot(engine, p) for p in part_ids}
+        cost["passes"] += 1; cost["advance_s"] += t1 - t0; cost["read_s"] += time.perf_counter() - t1
+        for p in part_ids:
+            on_step(p, s, prev[p], curs[p])
+            prev[p] = curs[p]
+    return prev
+
+
+def trees_identical(a, b):
+    return all(np.array_equal(getattr(a, f), getattr(b, f)) for f in _TOPO[1:] + _MUT + ("t", "mut_t")) and a.root == b.root
+
+
+def assert_stepped_chain_is_the_chain(make_engine, num_parts, moves):
+    """`make_engine()` -> a configured engine with a trace of at least `moves` rows.  `moves` passes of one move against one
+    pass of `moves` moves: traces and final trees bit for bit, the random streams at the same position."""
+    one, many = make_engine(), make_engine()
+    try:
+        dev = hasattr(one, "synchronize")
+        for _ in range(moves):
+            advance_one_move(one)
+        if dev:
+            many.run_moves_per_part(moves); many.synchronize()
+        else:
+            many.run_moves_per_part(moves, threads=1)
+        for p in range(num_parts):
+            s1, s2 = one.part_stats(p), many.part_stats(p)
+            assert s1["status"] == 0 and s2["status"] == 0
+            assert s1["moves_done"] == s2["moves_done"] == moves, (p, s1, s2)
+            assert s1["rng_draws"] == s2["rng_draws"], "part %d: rng draws %d stepped, %d in one pass" % (p, s1["rng_draws"], s2["rng_draws"])
+            assert s1["proposed"] == s2["proposed"] and s1["accepted"] == s2["accepted"], (p, s1, s2)
+            t1, t2 = one.part_trace(p, moves), many.part_trace(p, moves)
+            assert t1.shape == t2.shape == (moves, 4)
+            assert t1.tobytes() == t2.tobytes(), "part %d: the stepped trace differs from the pass's" % p
+            assert trees_identical(one.part_download(p), many.part_download(p)), "part %d: the stepped tree differs from the pass's" % p
+            n = s1["num_nodes"]
+            d1, d2 = one.part_derived(p, n), many.part_derived(p, n)
+            assert d1[0].tobytes() == d2[0].tobytes() and d1[2:] == d2[2:], "part %d: maintained totals differ" % p
+    finally:
+        one.close(); many.close()
+
+
+# ---- validity of a part's tree, in plain Python -----------------------------------------------------------------------
+def assert_valid_part(tree, ref):
+    """Links mutual; t_parent < t_mut <= t_child along every branch; every branch's mutations sorted by (t, site); every
+    mutation's `from` the state its site has just above it and no mutation on a site missing there; a tip inside
+    [t_min, t_max]; missing intervals sorted, disjoint and non-adjacent.  Raises AssertionError with the place."""
+    n, root = tree.num_nodes, int(tree.root)
+    par, c0, c1 = tree.parent.tolist(), tree.child0.tolist(), tree.child1.tolist()
+    t, tmin, tmax = tree.t.tolist(), tree.t_min.tolist(), tree.t_max.tolist()
+    mo, ms, mf, mt, mtt = tree.mut_offset.tolist(), tree.mut_site.tolist(), tree.mut_from.tolist(), tree.mut_to.tolist(), tree.mut_t.tolist()
+    io, s_, e_ = tree.miss_offset.tolist(), tree.miss_start.tolist(), tree.miss_end.tolist()
+    ref = np.asarray(ref).tolist()
+    assert 0 <= root < n and par[root] == -1, "root %d has parent %d" % (root, par[root])
+    seen = 0
+    for x in range(n):
+        assert (c0[x] < 0) == (c1[x] < 0), "node %d has one child" % x
+        for c in (c0[x], c1[x]):
+            if c >= 0:
+                assert 0 <= c < n and par[c] == x, "node %d lists child %d whose parent is %d" % (x, c, par[c])
+        if c0[x] >= 0:
+            assert c0[x] != c1[x], "node %d lists child %d twice" % (x, c0[x])
+        else:
+            # (t_min and t_max are stored in single precision; a tip without uncertainty keeps its date in double)
+            assert float(tmin[x]) <= t[x] <= float(tmax[x]) or (tmin[x] == tmax[x] and float(np.float32(t[x])) == tmin[x]), \
+                "tip %d at %r outside [%r, %r]" % (x, t[x], tmin[x], tmax[x])
+        if x != root:
+            P = par[x]
+            assert 0 <= P < n and x in (c0[P], c1[P]), "node %d names parent %d, which does not list it" % (x, P)
+            assert t[P] < t[x], "branch %d: t_parent %r >= t_child %r" % (x, t[P], t[x])
+            prev = None
+            for k in range(mo[x], mo[x + 1]):
+                assert t[P] < mtt[k] <= t[x], "branch %d: mutation at %r outside (%r, %r]" % (x, mtt[k], t[P], t[x])
+                assert prev is None or prev <= (mtt[k], ms[k]), "branch %d: mutations not sorted by (t, site)" % x
+                prev = (mtt[k], ms[k])
+        iv = [(s_[k], e_[k]) for k in range(io[x], io[x + 1])]
+        for k, (s, e) in enumerate(iv):
+            assert 0 <= s < e <= len(ref), "node %d: missing interval [%d, %d)" % (x, s, e)
+            assert k == 0 or iv[k - 1][1] < s, "node %d: missing intervals %s not sorted, disjoint and non-adjacent" % (x, iv)
+    # from-states and missing sites along every path: depth first with the states that differ from the ref's and the intervals
+    state, stack = {}, [(root, None)]
+    missing = []
+    while stack:
+        x, undo = stack.pop()
+        if undo is not None:
+            for l, old in reversed(undo[0]):
+                if old is None:
+                    state.pop(l, None)
+                else:
+                    state[l] = old
+            del missing[undo[1]:]
+            continue
+        seen += 1
+        log, nmiss = [], len(missing)
+        missing.extend((s_[k], e_[k]) for k in range(io[x], io[x + 1]))
+        for k in range(mo[x], mo[x + 1]):
+            l = ms[k]
+            cur = state.get(l, ref[l])
+            assert cur == mf[k], "node %d: mutation of site %d from %d, the path says %d" % (x, l, mf[k], cur)
+            assert mf[k] != mt[k], "node %d: mutation of site %d from %d to itself" % (x, l, mf[k])
+            assert not any(s <= l < e for s, e in missing), "node %d: mutation on the missing site %d" % (x, l)
+            log.append((l, state.get(l)))
+            state[l] = mt[k]
+        stack.append((x, (log, nmiss)))
+        for c in (c1[x], c0[x]):
+            if c >= 0:
+                stack.append((c, None))
+    assert seen == n, "%d of %d nodes hang on the root" % (seen, n)
+
+
+# ---- the per-move checks ----------------------------------------------------------------------------------------------
+class Coverage:
+    """What the checked steps of a test file amount to (the conditions of the issue are asserted on the sum over its cases)."""
+    FIELDS = ("steps", "accepted", "accepted_root_displacements", "accepted_negative_log_mh", "accepted_while_grid_grew",
+              "accepted_reform_same_site_twice", "accepted_reform_more_than_32", "accepted_outside_root_part", "compound", "compound_accepted",
+              "rejected_topology", "rejected_rooty_not_bit_identical", "rejected_topology_lambda_not_bit_identical", "unchecked")
+
+    def __init__(self):
+        self.steps = 0
+        self.accepted = [0] * 5
+        self.accepted_negative_log_mh = [0] * 3
+        self.accepted_root_displacements = self.accepted_while_grid_grew = self.accepted_reform_same_site_twice = 0
+        self.accepted_reform_more_than_32 = self.accepted_outside_root_part = self.compound = self.compound_accepted = 0
+        self.rejected_topology = self.rejected_rooty_not_bit_identical = self.rejected_topology_lambda_not_bit_identical = self.unchecked = 0
+
+    def add(self, o):
+        for f in self.FIELDS:
+            a, b = getattr(self, f), getattr(o, f)
+            setattr(self, f, [x + y for x, y in zip(a, b)] if isinstance(a, list) else a + b)
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def assert_conditions(self):
+        d = self.as_dict()
+        assert self.unchecked == 0, d
+        assert min(self.accepted) >= 50, d
+        assert self.accepted_root_displacements >= 20, d
+        assert min(self.accepted_negative_log_mh) >= 20, d
+        assert self.accepted_while_grid_grew >= 1, d
+        assert self.accepted_reform_same_site_twice >= 1, d
+        assert self.accepted_reform_more_than_32 >= 1, d
+        assert self.accepted_outside_root_part >= 100, d
+
+
+class PartWatch:
+    """The exact side of one part's chain: the model, the Derived of the tree it holds and its exact k_bar_p, carried from move
+    to move (a move's `before` is the last move's `after`)."""
+
+    def __init__(self, p, first, ref, ev, pop, includes_root, tag=""):
+        self.p, self.ref, self.ev, self.pop, self.includes_root, self.tag = p, np.asarray(ref), ev, pop, bool(includes_root), tag
+        self.dv = X.Derived(first["tree"], ref, ev)
+        tab = first["tab"]
+        self.kb = X.k_bar_p(self.dv.T, self.includes_root, tab["t_ref"], tab["t_step"], len(tab["k_bar_p"]))[0]
+        self.kbf = np.array([abs(float(k)) for k in self.kb])      # |k_bar_p| as floats, for the allowance's kmax
+        self.moves = 0          # since k_bar_p was built from scratch
+        assert_valid_part(first["tree"], ref)
+
+    def k_allowance(self, tab):
+        """check_part's allowance for a maintained k_bar_p after `moves` moves (test_exact_model.py)."""
+        kmax = max(1.0, float(self.kbf.max()))
+        bmax = (abs(tab["t_ref"]) + len(self.kb) * tab["t_step"]) / tab["t_step"]
+        return min(4 * self.moves * X.U * (kmax + bmax), 1e-9 * kmax)
+
+
+def _slices(tree, x):
+    a, b = int(tree.mut_offset[x]), int(tree.mut_offset[x + 1])
+    return tree.mut_site[a:b].tolist(), tree.mut_from[a:b].tolist(), tree.mut_to[a:b].tolist(), tree.mut_t[a:b].tolist()
+
+
+def _same_except(a, b, fields, what, fails, where):
+    for f in fields:
+        x, y = getattr(a, f), getattr(b, f)
+        if not (np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y):
+            fails.append("%s: %s changed %s" % (where, what, f))
+
+
+def _bits(x):
+    return np.asarray(x, np.float64).tobytes()
+
+
+def check_step(tally, cov, w: PartWatch, step, b, a):
+    """One move of part w.p: `b` and `a` are snapshots before and after it.  Failures go to tally.fail; a step that could not be
+    checked counts in cov.unchecked (and is a failure)."""
+    where = "%s part %d step %d" % (w.tag, w.p, step)
+    fails = tally.fail
+    n0 = len(fails)
+    cov.steps += 1
+    w.moves += 1
+    tb, ta, tabb, taba = b["tree"], a["tree"], b["tab"], a["tab"]
+    try:
+        if a["stats"]["status"] != 0 or a["stats"]["moves_done"] != b["stats"]["moves_done"] + 1 or a["trace_len"] != b["trace_len"] + 1:
+            fails.append("%s: status %d, moves_done %d -> %d, trace %d -> %d rows" % (where, a["stats"]["status"], b["stats"]["moves_done"], a["stats"]["moves_done"], b["trace_len"], a["trace_len"]))
+            cov.unchecked += 1
+            return
+        kind, node, acc, log_mh = int(a["row"][0]), int(a["row"][1]), a["row"][2] == 1.0, float(a["row"][3])
+        if not (0 <= kind < 5 and a["row"][2] in (0.0, 1.0)):
+            fails.append("%s: trace row %s" % (where, a["row"])); cov.unchecked += 1
+            return
+        where += " (%s of node %d, %s, log_mh %r)" % (KINDS[kind], node, "accepted" if acc else "not accepted", log_mh)
+        dp = [y - x for x, y in zip(b["stats"]["proposed"], a["stats"]["proposed"])]
+        da = [y - x for x, y in zip(b["stats"]["accepted"], a["stats"]["accepted"])]
+        if dp != [int(k == kind) for k in range(5)] or da != [int(k == kind and acc) for k in range(5)]:
+            fails.append("%s: proposed rose by %s, accepted by %s" % (where, dp, da))
+        if acc and not (log_mh == log_mh):
+            fails.append("%s: accepted with a NaN log_mh" % where)
+        grew = len(taba["k_bar_p"]) - len(tabb["k_bar_p"])
+        if grew < 0 or (grew and not w.includes_root):
+            fails.append("%s: the grid went from %d to %d cells" % (where, len(tabb["k_bar_p"]), len(taba["k_bar_p"])))
+        if grew > 0:
+            w.kb.extend([F(1)] * grew)          # appended cells hold the lineage above the root and nothing else
+            w.kbf = np.concatenate([w.kbf, np.ones(grew)])
+        compound = kind == 2 and w.includes_root and node >= 0 and node != tb.root and int(tb.parent[node]) == tb.root
+        nb = len(tabb["k_bar_p"])
+
+        if not acc and not compound:
+            if kind >= 3:
+                cov.rejected_topology += 1
+            if _bits(a["G"]) != _bits(b["G"]) or _bits(a["A"]) != _bits(b["A"]):
+                fails.append("%s: totals changed: log_G %r -> %r, log_aug_prior %r -> %r" % (where, b["G"], a["G"], b["A"], a["A"]))
+            if _bits(taba["k_bar_p"][:nb]) != _bits(tabb["k_bar_p"]) or not np.all(taba["k_bar_p"][nb:] == 1.0):
+                fails.append("%s: k_bar_p changed" % where)
+            if kind >= 3:       # a pruned subtree goes back under its old parent, in either of its two slots
+                _same_except(tb, ta, tuple(f for f in _TOPO if f not in ("child0", "child1")) + _MUT, "a move that was not accepted", fails, where)
+                if not (np.array_equal(np.minimum(ta.child0, ta.child1), np.minimum(tb.child0, tb.child1)) and np.array_equal(np.maximum(ta.child0, ta.child1), np.maximum(tb.child0, tb.child1))):
+                    fails.append("%s: a move that was not accepted changed a node's children" % where)
+            else:
+                _same_except(tb, ta, _TOPO + _MUT, "a move that was not accepted", fails, where)
+            if _bits(ta.t) != _bits(tb.t):
+                fails.append("%s: node times changed" % where)
+            rooty = kind >= 3 and w.includes_root and node >= 0 and node != tb.root and int(tb.parent[node]) == tb.root
+            if rooty and (_bits(ta.mut_t) != _bits(tb.mut_t) or _bits(a["lam"]) != _bits(b["lam"])):
+                # pruned from under the run's root: the sibling's mutations were reflected about the root's time and back,
+                # t -> t_P - (t - t_P) -> t_P + (t_P - t'), four roundings; and the root's lambda was recomputed from its child's
+                root = tb.root
+                S = int(tb.child1[root]) if int(tb.child0[root]) == node else int(tb.child0[root])
+                lo, hi = int(tb.mut_offset[S]), int(tb.mut_offset[S + 1])
+                keep = np.ones(tb.mut_t.shape[0], bool); keep[lo:hi] = False
+                tP = float(tb.t[root])
+                if ta.mut_t[keep].tobytes() != tb.mut_t[keep].tobytes() or \
+                        not np.all(np.abs(ta.mut_t[lo:hi] - tb.mut_t[lo:hi]) <= 4 * X.U * (abs(tP) + np.abs(tb.mut_t[lo:hi] - tP))):
+                    fails.append("%s: mutation times changed beyond the sibling's reflection about the root" % where)
+                other = np.ones(tb.num_nodes, bool); other[root] = False
+                if a["lam"][other].tobytes() != b["lam"][other].tobytes() or not np.array_equal(a["nsm"], b["nsm"]):
+                    fails.append("%s: lambda_i changed below the root" % where)
+                tally.check("lambda_root_after_rejected_move", w.dv.lambda_i(root), a["lam"][root], where)
+                w.dv = w.dv.retimed(ta)
+                cov.rejected_rooty_not_bit_identical += 1
+                return
+            if _bits(ta.mut_t) != _bits(tb.mut_t):
+                fails.append("%s: mutation times changed" % where)
+            if not np.array_equal(a["nsm"], b["nsm"]):
+                fails.append("%s: num_sites_missing changed" % where)
+            if _bits(a["lam"]) != _bits(b["lam"]):
+                if kind < 3:
+                    fails.append("%s: lambda_i changed" % where)
+                else:       # hopping the pruned subtree up and down the tree recomputes the lambda of the nodes it passes
+                    cov.rejected_topology_lambda_not_bit_identical += 1
+                    for x in np.flatnonzero(a["lam"] != b["lam"]).tolist():
+                        tally.check("lambda_i_after_rejected_move", w.dv.lambda_i(x), a["lam"][x], "%s node %d" % (where, x))
+            if len(fails) > n0:
+                w.dv = X.Derived(ta, w.ref, w.ev)
+            return
+
+        # ---- the state changed (or may have: an accepted branch reform of a branch without mutations changes nothing) --------
+        simple = kind <= 2 and not compound
+        if simple:
+            # locality first: the exact side then re-reads only the times
+            _same_except(tb, ta, _TOPO, "a %s" % KINDS[kind], fails, where)
+            if _bits(a["lam"]) != _bits(b["lam"]) or not np.array_equal(a["nsm"], b["nsm"]):
+                fails.append("%s: lambda_i or num_sites_missing changed" % where)
+            if kind <= 1:
+                _same_except(tb, ta, _MUT, "a displacement", fails, where)
+                if _bits(ta.mut_t) != _bits(tb.mut_t):
+                    fails.append("%s: a displacement changed mutation times" % where)
+                diff = np.flatnonzero(ta.t != tb.t).tolist()
+                if diff != [node]:
+                    fails.append("%s: node times changed at %s" % (where, diff))
+                if (ta.child0[node] < 0) != (kind == 1):
+                    fails.append("%s: node %d is %s" % (where, node, "a tip" if ta.child0[node] < 0 else "an inner node"))
+            else:
+                if _bits(ta.t) != _bits(tb.t):
+                    fails.append("%s: a branch reform changed node times" % where)
+                lo, hi = int(tb.mut_offset[node]), int(tb.mut_offset[node + 1])
+                keep = np.ones(tb.mut_t.shape[0], bool); keep[lo:hi] = False
+                for f in _MUT + ("mut_t",):
+                    if getattr(ta, f)[keep].tobytes() != getattr(tb, f)[keep].tobytes():
+                        fails.append("%s: a branch reform changed %s of another branch" % (where, f))
+                sb_, fb_, ob_, _ = _slices(tb, node)
+                sa_, fa_, oa_, _ = _slices(ta, node)
+                if sorted(zip(sb_, fb_, ob_)) != sorted(zip(sa_, fa_, oa_)):
+                    fails.append("%s: the branch's mutations changed as a multiset of (site, from, to)" % where)
+                for l in set(sb_):
+                    if [(f, o) for s, f, o in zip(sb_, fb_, ob_) if s == l] != [(f, o) for s, f, o in zip(sa_, fa_, oa_) if s == l]:
+                        fails.append("%s: the mutations of site %d changed their order" % (where, l))
+                if len(set(sb_)) < len(sb_):
+                    cov.accepted_reform_same_site_twice += 1
+                if len(sb_) > 32:
+                    cov.accepted_reform_more_than_32 += 1
+            if len(fails) > n0:
+                cov.unchecked += 1          # the exact side below relies on the locality just refuted
+                w.dv = X.Derived(ta, w.ref, w.ev)
+                w.kb = X.k_bar_p(w.dv.T, w.includes_root, taba["t_ref"], taba["t_step"], len(taba["k_bar_p"]))[0]
+                w.kbf = np.array([abs(float(k)) for k in w.kb])
+                return
+            dvA = w.dv.retimed(ta)
+        else:
+            dvA = X.Derived(ta, w.ref, w.ev)
+            tally.equal("num_sites_missing", a["nsm"], dvA.nsm, where)
+        assert_valid_part(ta, w.ref)
+
+        dG = X.part_log_G_delta(w.dv, dvA, w.ref, w.ev, w.includes_root)
+        dP = X.partial_log_prior_delta(w.dv.T, dvA.T, w.pop, w.includes_root, taba)
+        for i, (kB, kA) in dP.cells.items():
+            if w.kb[i] != kB:
+                fails.append("%s: the exact k_bar_p carried from move to move is off at cell %d" % (where, i)); cov.unchecked += 1
+            w.kb[i] = kA; w.kbf[i] = abs(float(kA))
+        k_term = float(dP.k_sensitivity) * w.k_allowance(taba)
+
+        # the increments of the maintained totals, all five kinds
+        tally.check("increment_log_G", dG, F(a["G"]) - F(b["G"]), where, 2 * X.U * max(abs(b["G"]), abs(a["G"])))
+        tally.check("increment_log_aug_prior", dP, F(a["A"]) - F(b["A"]), where, 2 * X.U * max(abs(b["A"]), abs(a["A"])) + k_term)
+
+        if compound:
+            cov.compound += 1
+            cov.compound_accepted += int(acc)
+        elif kind <= 1:
+            root_move = node == tb.root
+            if root_move:
+                cov.accepted_root_displacements += 1
+                ex = X.Exact(dG.value + dP.value, dG.S + dP.S, dG.n + dP.n)
+                tally.check("log_mh_root_displace", ex, log_mh, where, k_term)
+            else:
+                slope = X.displacement_slope(w.dv, node)
+                lin = slope * (F(float(ta.t[node])) - F(float(tb.t[node])))
+                if dG.value != lin:
+                    fails.append("%s: log G is not linear in the node's time: exact difference %r, slope x step %r" % (where, float(dG.value), float(lin)))
+                ex = X.Exact(dP.value, dP.S + 2 * abs(lin), dP.n + 2)
+                tally.check("log_mh_%s" % KINDS[kind], ex, log_mh, where, k_term)
+        elif kind == 2:
+            tally.check("log_mh_branch_reform", dG, log_mh, where)
+            if dP.cells or dP.value != 0 or _bits(a["A"]) != _bits(b["A"]) or _bits(taba["k_bar_p"]) != _bits(tabb["k_bar_p"]):
+                fails.append("%s: a branch reform touched the prior or k_bar_p" % where)
+        # (subtree slide, SPR1: the proposal-density part of log_mh is out of scope; their increments are checked above)
+
+        if acc:
+            cov.accepted[kind] += 1
+            if simple and log_mh < 0.0:
+                cov.accepted_negative_log_mh[kind] += 1
+            if grew > 0:
+                cov.accepted_while_grid_grew += 1
+            if not w.includes_root:
+                cov.accepted_outside_root_part += 1
+        w.dv = dvA
+    except AssertionError as e:
+        fails.append("%s: %s" % (where, e))
+        cov.unchecked += 1
+
+
+def run_stepped(tally, cov, engine, sc, parts, incl, ref, ev, pop, steps, tag="", watch=None, advance=advance_one_move):
+    """Step a configured engine `steps` times and check every move of the watched parts (default: all)."""
+    ids = list(range(len(parts))) if watch is None else list(watch)
+    if hasattr(engine, "synchronize"):
+        engine.synchronize()
+    watches = {}
+
+    def on_step(p, s, before, after):
+        if p not in watches:
+            watches[p] = PartWatch(p, before, ref, ev, pop, incl[p], tag)
+        check_step(tally, cov, watches[p], s, before, after)
+    step_chain(engine, ids, steps, on_step, advance)
+    return watches
