@@ -26,7 +26,7 @@ emat_status emat_debug_slab_layout(emat_backend* h, int32_t part_id, uint32_t* o
   const int trace_cap = h->cfg.trace_moves > 0 ? h->cfg.trace_moves : 0;
   const uint32_t content = heap_content_bytes(ph.tree);
   const SlabGeo g = slab_geometry(h, ph.tree.num_nodes(), ph.tree.num_muts(), content, (int)ph.coal.k_bar_p.size(), ph.includes_run_root, ph.space_boost, ph.cell_boost);
-  out8[0] = (uint32_t)sizeof(SlabHeader); out8[1] = (uint32_t)ph.tree.num_nodes() * (uint32_t)sizeof(NodeRec); out8[2] = a16((uint32_t)g.cell_cap * cell_bytes_for(ph.includes_run_root));
+  out8[0] = (uint32_t)sizeof(SlabHeader); out8[1] = (uint32_t)ph.tree.num_nodes() * (uint32_t)sizeof(NodeRec) + miss_dl_bytes_for((uint32_t)ph.tree.num_nodes()); out8[2] = a16((uint32_t)g.cell_cap * cell_bytes_for(ph.includes_run_root));
   out8[3] = a16((uint32_t)trace_cap * 32u); out8[4] = content; out8[5] = g.heap; out8[6] = g.scratch; out8[7] = (uint32_t)g.cell_cap;
   return EMAT_OK;
 }
@@ -100,6 +100,17 @@ emat_status emat_debug_tree_query(emat_backend* h, int32_t part_id, int32_t op, 
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return EMAT_OK;
+}
+/* test hook (header: emat_debug_miss_dl_check) */
+emat_status emat_debug_miss_dl_check(emat_backend* h, int32_t* out_2n) {
+  if (!h || !out_2n) return EMAT_ERR_INVALID_ARGUMENT;
+  if (h->host_only) return no_device(h);
+  if (!bind_device(h)) return fail(h, EMAT_ERR_HIP, "hipSetDevice failed");
+  if (h->parts.empty()) return EMAT_OK;
+  emat_status st = debug_settle(h, false); if (st) return st;   // (no recalculation: it would forget what is to be checked)
+  DevBuf<int32_t> dout;
+  HIP_TRY(dout.alloc(2 * h->parts.size()));
+  return run_over_parts(h, k_debug_miss_dl_check, dout.p, out_2n, 2 * h->parts.size(), dout.p);
 }
 /* test hook (header: emat_debug_graft) */
 emat_status emat_debug_graft(emat_backend* h, int32_t part_id, int32_t X, double mu_proposal, int32_t mode, int32_t new_sibling, double new_t_P,

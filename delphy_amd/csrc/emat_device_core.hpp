@@ -438,6 +438,9 @@ EMAT_D void swap_lists(ListRef& a, ListRef& b) { ListRef t = a; a = b; b = t; }
 EMAT_D MutRec* muts_of(Ctx& c, int n) { return (MutRec*)heap_at(c, nodes_of(c)[n].muts.off); }
 EMAT_D IvRec* miss_of(Ctx& c, int n) { return (IvRec*)heap_at(c, nodes_of(c)[n].miss.off); }
 EMAT_D FsRec* mfs_of(Ctx& c, int n) { return (FsRec*)heap_at(c, nodes_of(c)[n].mfs.off); }
+// the nodes' remembered missation rate changes (emat_slab.hpp; delta_lambda_across_node_missations below)
+EMAT_DF uint64_t* miss_dl_of(const Ctx& c) { return (uint64_t*)(nodes_of(c) + hdr_of(c)->n_nodes); }
+EMAT_DF void miss_dl_forget(Ctx& c, int node) { miss_dl_of(c)[node] = k_miss_dl_unknown; }   // the node's `miss` or `mfs` list is being written
 EMAT_D int nmuts(const Ctx& c, int n) { return (int)nodes_of(c)[n].muts.cnt; }
 EMAT_D bool is_tip(const Ctx& c, int n) { return nodes_of(c)[n].child0 == k_no_node; }
 EMAT_D int sibling_of(Ctx& c, int parent, int x) {
@@ -561,6 +564,7 @@ EMAT_DN void miss_set_from_state(Ctx& c, int node, int l, int from) {
   int k = fs_lower_bound(v, n, l);
   bool present = (k < n && v[k].site == l);
   if (from != (int)c.ref[l]) {
+    miss_dl_forget(c, node);
     if (present) { v[k].state = (uint8_t)from; return; }
     list_reserve<FsRec>(c, r, n + 1);
     if (c.failed) return;
@@ -569,6 +573,7 @@ EMAT_DN void miss_set_from_state(Ctx& c, int node, int l, int from) {
     v[k].site = l; v[k].state = (uint8_t)from; v[k].pad[0] = v[k].pad[1] = v[k].pad[2] = 0;
     set_list_cnt(c, r, n + 1);
   } else if (present) {
+    miss_dl_forget(c, node);
     for (int i = k; i + 1 < n; ++i) v[i] = v[i + 1];
     set_list_cnt(c, r, n - 1);
   }
@@ -618,14 +623,28 @@ EMAT_D double delta_lambda_across_missations(Ctx& c, const IvRec* iv, int niv, c
   for (int i = 0; i < nfs; ++i) { int l = fs[i].site; r -= mu_of(c)[site_part(c, l)] * site_nu(c, l) * (q_a(c, l, fs[i].state) - q_a(c, l, c.ref[l])); }
   return r;
 }
-EMAT_D double delta_lambda_across_node_missations(Ctx& c, int node) {
+EMAT_D double delta_lambda_across_node_missations_fresh(Ctx& c, int node) {
   return delta_lambda_across_missations(c, miss_of(c, node), (int)nodes_of(c)[node].miss.cnt, mfs_of(c, node), (int)nodes_of(c)[node].mfs.cnt);
 }
-EMAT_D double delta_lambda_across_branch(Ctx& c, int node) {   // h:140-155
+// The same number, remembered per node (k_miss_dl_unknown, emat_slab.hpp): two cumQ gathers per interval and a reference-sequence
+// load per from-state, all dependent and all on the chain's critical path, for a value that only a topology move can change.  What is
+// stored is what the function above returned for the node's lists as they are, so a hit and a miss hand out the same bits.
+EMAT_D double delta_lambda_across_node_missations(Ctx& c, int node) { EMAT_TIMED(0);   /* miss_dl: every request */
+  uint64_t* e = miss_dl_of(c) + node;
+  const uint64_t bits = *e;
+  if (bits != k_miss_dl_unknown) return __longlong_as_double((long long)bits);
+  double r;
+  { EMAT_TIMED(0);   /* miss_dl: not known, computed (1 - calls of this scope / calls of the one above = the hit rate) */
+    r = delta_lambda_across_node_missations_fresh(c, node); }
+  *e = (uint64_t)__double_as_longlong(r);
+  return r;
+}
+// kMemo = false: every lane of a whole-part recomputation asks for its own nodes, and leaves the remembered values alone
+template <bool kMemo = true> EMAT_D double delta_lambda_across_branch(Ctx& c, int node) {   // h:140-155
   double r = 0.0;
   const MutRec* m = muts_of(c, node); int nm = nmuts(c, node);
   for (int i = 0; i < nm; ++i) { int l = m[i].site; r += mu_of(c)[site_part(c, l)] * site_nu(c, l) * (q_a(c, l, m[i].to) - q_a(c, l, m[i].from)); }
-  r += delta_lambda_across_node_missations(c, node);
+  r += kMemo ? delta_lambda_across_node_missations(c, node) : delta_lambda_across_node_missations_fresh(c, node);
   return r;
 }
 EMAT_DN double calc_lambda_at_node(Ctx& c, int node) {   // cpp:406-418

@@ -73,6 +73,7 @@ EMAT_DN void node_merge_missations_from(Ctx& c, int dst, int other) {
       else if (i == fa || B[j].site < A[i].site) fs.p[fs.n++] = B[j++];
       else { fs.p[fs.n++] = A[i++]; ++j; }   // map::insert keeps the first
     }
+    miss_dl_forget(c, dst);
     list_assign<IvRec>(c, nodes_of(c)[dst].miss, iv.p, iv.n);
     list_assign<FsRec>(c, nodes_of(c)[dst].mfs, fs.p, fs.n);
   }
@@ -98,6 +99,7 @@ EMAT_DN void node_factor_out_common(Ctx& c, int a, int b, int common) {
     }
     while (i < fa) fca.p[fca.n++] = A[i++];
     while (j < fb) fcb.p[fcb.n++] = B[j++];
+    miss_dl_forget(c, a); miss_dl_forget(c, b); miss_dl_forget(c, common);
     list_assign<IvRec>(c, nodes_of(c)[a].miss, ia.p, ia.n); list_assign<FsRec>(c, nodes_of(c)[a].mfs, fca.p, fca.n);
     list_assign<IvRec>(c, nodes_of(c)[b].miss, ib.p, ib.n); list_assign<FsRec>(c, nodes_of(c)[b].mfs, fcb.p, fcb.n);
     list_assign<IvRec>(c, nodes_of(c)[common].miss, ic.p, ic.n); list_assign<FsRec>(c, nodes_of(c)[common].mfs, fcc.p, fcc.n);
@@ -199,6 +201,7 @@ EMAT_DF void edit_do_hop_up(Ctx& c, int X) {   // tree_editing.cpp:164-231
     node_merge_missations_from(c, S, P);
     nodes_of(c)[P].miss.cnt = 0; nodes_of(c)[P].mfs.cnt = 0;
   }
+  miss_dl_forget(c, P); miss_dl_forget(c, G);   // (P's lists emptied and then exchanged with G's)
   swap_lists(nodes_of(c)[P].muts, nodes_of(c)[G].muts);
   swap_lists(nodes_of(c)[P].miss, nodes_of(c)[G].miss);
   swap_lists(nodes_of(c)[P].mfs, nodes_of(c)[G].mfs);
@@ -232,6 +235,7 @@ EMAT_DN void edit_flip(Ctx& c, const Edit e) {   // tree_editing.cpp:233-278 (re
     node_merge_missations_from(c, S, P);
     node_merge_missations_from(c, X, P);
     nodes_of(c)[P].miss.cnt = 0; nodes_of(c)[P].mfs.cnt = 0;
+    miss_dl_forget(c, P);
   }
   if (iv_intersects(miss_of(c, X), (int)nodes_of(c)[X].miss.cnt, miss_of(c, U), (int)nodes_of(c)[U].miss.cnt)) node_factor_out_common(c, X, U, P);
   nodes_of(c)[G].child0 = S; nodes_of(c)[G].child1 = P;
@@ -692,7 +696,7 @@ EMAT_DN void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1)
   EMAT_TIMED_END(setup_timer);
   double next_pl_B;
   { EMAT_TIMED(1);   /* start_inner: first delta_lambda_across_missations */
-  next_pl_B = -1 * delta_lambda_across_missations(c, sl_iv.p, sl_iv.n, sl_fs.p, sl_fs.n); }
+  next_pl_B = -1 * delta_lambda_across_node_missations(c, S); }   // (the sliding sets still are S's own lists, entry for entry)
   g.bi[0].pl_A -= next_pl_B;
   int cur = P, parent = nodes_of(c)[cur].parent, sibling = sibling_of(c, parent, cur);
   double partial_lambda = next_pl_B;

@@ -313,6 +313,7 @@ __global__ void __launch_bounds__(k_wave) k_gt_build(GTreeDev g, GPartition pt, 
   SlabHeader* H = (SlabHeader*)slab;
   uint32_t off = (uint32_t)sizeof(SlabHeader);
   const uint32_t off_nodes = off; off += (uint32_t)n * (uint32_t)sizeof(NodeRec);
+  { uint64_t* dl = (uint64_t*)(slab + off); for (int i = lane; i < n; i += k_wave) dl[i] = k_miss_dl_unknown; off += miss_dl_bytes_for((uint32_t)n); }
   const bool root_part = (d.flags & k_flag_includes_run_root) != 0;
   const uint32_t off_cells = off; off += gt_a16((uint32_t)d.cell_cap * (root_part ? k_cell_bytes_root : k_cell_bytes_own));
   const uint32_t off_trace = off; off += gt_a16((uint32_t)d.trace_cap * 32u);

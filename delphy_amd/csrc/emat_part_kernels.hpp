@@ -486,8 +486,11 @@ template <bool kCheck> __device__ __forceinline__ void recalc_derived_body(const
   auto NMISS = [&](int i) -> int32_t& { return kCheck ? nmiss_of[i] : c.N[i].n_missing; };
   // phase A: per-branch deltas
   for (int i = lane; i < n; i += k_wave) {
-    LAM(i) = dev::delta_lambda_across_branch(c, i);
+    // <false>: without the nodes' remembered values -- the check must leave the slab as it is, and the recalculation forgets them below
+    LAM(i) = dev::delta_lambda_across_branch<false>(c, i);
     NMISS(i) = dev::iv_num_sites(dev::miss_of(c, i), (int)c.N[i].miss.cnt);
+    // what the moves remembered of the nodes' missation rate changes (emat_slab.hpp) may belong to another model or reference sequence
+    if (!kCheck) dev::miss_dl_forget(c, i);
   }
   __syncthreads();
   // phase B: pre-order prefix (phylo_tree_calc.cpp:420-436, :67-76)
@@ -557,6 +560,28 @@ template <bool kCheck> __device__ __forceinline__ void recalc_derived_body(const
 }
 __global__ void __launch_bounds__(k_wave) k_recalc_derived(KernelArgs a) { recalc_derived_body<false>(a, nullptr); }
 __global__ void __launch_bounds__(k_wave) k_check_derived(KernelArgs a, double* check_out) { recalc_derived_body<true>(a, check_out); }
+// test hook (emat_debug_miss_dl_check): the remembered missation rate change of every node (emat_slab.hpp) against a fresh evaluation
+// of the same function on the node's lists as they stand.  out[2 part] = entries that are known and differ from it in bits,
+// out[2 part + 1] = entries that are known.
+__global__ void __launch_bounds__(k_wave) k_debug_miss_dl_check(KernelArgs a, int32_t* out) {
+  __shared__ __attribute__((aligned(16))) double lds_tables[k_lds_tables_bytes / 8];
+  const int lane = threadIdx.x;
+  const int part = blockIdx.x;
+  uint8_t* slab = a.slabs + a.slab_off[part];
+  const double* tables = stage_tables(a, lds_tables, lane);
+  __syncthreads();
+  dev::Ctx c;
+  init_ctx(c, slab, slab, a, tables);
+  int bad = 0, known = 0;
+  for (int i = lane; i < c.H->n_nodes; i += k_wave) {
+    const uint64_t bits = dev::miss_dl_of(c)[i];
+    if (bits == k_miss_dl_unknown) continue;
+    ++known;
+    if (bits != (uint64_t)__double_as_longlong(dev::delta_lambda_across_node_missations_fresh(c, i))) ++bad;
+  }
+  for (int off = 32; off > 0; off >>= 1) { bad += __shfl_down(bad, off, k_wave); known += __shfl_down(known, off, k_wave); }
+  if (lane == 0) { out[2 * part] = bad; out[2 * part + 1] = known; }
+}
 // test hook (emat_debug_tree_query): the moves' own find_MRCA_of / descends_from on one part's slab, query by query
 __global__ void __launch_bounds__(k_wave) k_debug_tree_query(KernelArgs a, int part, int op, const int32_t* qa, const int32_t* qb, int32_t* out, int n) {
   if (threadIdx.x != 0) return;

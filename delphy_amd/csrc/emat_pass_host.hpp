@@ -166,6 +166,7 @@ emat_status materialize(emat_backend* h) {
       NodeRec* N = (NodeRec*)(h->h_slabs.data() + ph.slab_off + H->off_nodes);
       for (int i = 0; i < H->n_nodes; ++i) { N[i].lambda = ph.kept_lambda[(size_t)i]; N[i].n_missing = ph.kept_n_missing[(size_t)i]; }
       H->log_G = ph.kept_log_G; H->log_aug_prior = ph.kept_log_aug_prior;
+      if ((int)ph.kept_miss_dl.size() == H->n_nodes) std::memcpy(N + H->n_nodes, ph.kept_miss_dl.data(), (size_t)H->n_nodes * 8);   // (bits, the "not known" ones included)
     } else ph.derived_kept = false;
   });
   bool all_kept = !h->parts.empty();
@@ -454,6 +455,7 @@ emat_status finish_pass(emat_backend* h) {
         const SlabHeader* H = (const SlabHeader*)slab; const NodeRec* N = (const NodeRec*)(slab + H->off_nodes);
         ph.kept_lambda.resize((size_t)H->n_nodes); ph.kept_n_missing.resize((size_t)H->n_nodes);
         for (int i = 0; i < H->n_nodes; ++i) { ph.kept_lambda[(size_t)i] = N[i].lambda; ph.kept_n_missing[(size_t)i] = N[i].n_missing; }
+        { const uint64_t* dl = (const uint64_t*)(N + H->n_nodes); ph.kept_miss_dl.assign(dl, dl + H->n_nodes); }
         ph.kept_log_G = H->log_G; ph.kept_log_aug_prior = H->log_aug_prior; ph.derived_kept = true;
       });
     }

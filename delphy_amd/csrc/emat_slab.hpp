@@ -8,7 +8,7 @@
 // A slab is ONE relocatable byte blob per part (all internal references are byte offsets), so that a
 // workgroup can stream it into LDS with one coalesced copy, run its chain there, and stream it back:
 //
-//   [SlabHeader 256 B][NodeRec x n_nodes (64 B each)][cell table (2 arrays x cell_cap; the root part: 6 arrays)]
+//   [SlabHeader 256 B][NodeRec x n_nodes (64 B each)][missation rate change x n_nodes (8 B each)][cell table (2 arrays x cell_cap; the root part: 6 arrays)]
 //   [trace ring][list heap: 16-B mutation / 8-B interval / 8-B from-state records][scratch]
 //
 // Plain C++ (no HIP types) because the host encoder and the kernels share it.
@@ -80,6 +80,16 @@ struct NodeRec {    // 64 B = one cache line per node
   double t;
   double lambda;      // lambda_i_[node]
 };
+// Beside the node records, one double per node: the rate change across the node's own missations (its `miss` intervals and `mfs`
+// from-states; delta_lambda_across_missations, emat_device_core.hpp), remembered from the last time a move asked for it.  It is a
+// pure function of those two lists and of tables that stay the same while parts run, so it holds until a topology move edits the
+// lists: every device function that writes them puts k_miss_dl_unknown back (miss_dl_forget), as do both encoders and
+// k_recalc_derived, and whoever wants the value then computes it -- with the same function on the same operands, so the bits every
+// consumer sees are the ones it would have computed itself.  The array follows the node records (slab byte off_nodes + 64 n_nodes),
+// is staged with them and is part of what a mid-pass re-materialisation carries over (PartHost::kept_miss_dl).
+// "Not known" is a NaN of a bit pattern no arithmetic produces; entries are compared as bits, never as values.
+constexpr uint64_t k_miss_dl_unknown = 0x7FF8454D41544D44ull;
+constexpr uint32_t miss_dl_bytes_for(uint32_t n_nodes) { return (n_nodes * 8u + 15u) & ~15u; }   // (constexpr: host and device)
 static_assert(sizeof(ListRef) == 8, "ListRef must be 8 bytes");
 static_assert(sizeof(MutRec) == 16, "MutRec must be 16 bytes");
 static_assert(sizeof(NodeRec) == 64, "NodeRec must be 64 bytes");

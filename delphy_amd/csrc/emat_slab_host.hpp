@@ -20,6 +20,7 @@ void encode_slab(const PartHost& ph, uint8_t* slab, uint32_t slab_bytes, uint32_
   H->status = 0; H->rng_key = ph.rng.key; H->rng_counter = ph.rng.counter; H->rng_spare = ph.rng.spare; H->rng_has_spare = ph.rng.has_spare ? 1u : 0u;
   uint32_t off = sizeof(SlabHeader);
   H->off_nodes = off; off += (uint32_t)n * (uint32_t)sizeof(NodeRec);
+  { uint64_t* dl = (uint64_t*)(slab + off); for (int i = 0; i < n; ++i) dl[i] = k_miss_dl_unknown; off += miss_dl_bytes_for((uint32_t)n); }   // nothing remembered: the moves fill it in as they ask
   H->off_cells = off; off += a16((uint32_t)cell_cap * cell_bytes_for(ph.includes_run_root));
   H->off_trace = off; off += a16((uint32_t)trace_cap * 32u);
   H->heap_begin = off; H->heap_end = off + heap_bytes;
@@ -118,7 +119,7 @@ SlabGeo slab_geometry(const emat_backend* h, int n, int num_muts, uint32_t conte
   const uint32_t regions_max = (uint32_t)n + (uint32_t)num_muts;
   g.scratch = a16((uint32_t)(space_boost * std::max<uint32_t>(8192u, 128u * regions_max + 4u * content + 256u * (uint32_t)n)));
   g.cell_cap = includes_run_root ? nc + cell_boost * std::max(512, nc) : nc;   // room for the root part's grid to grow into the past (a part that outgrows it stops with status 103 / 105)
-  g.bytes = (uint32_t)sizeof(SlabHeader) + (uint32_t)n * (uint32_t)sizeof(NodeRec) + a16((uint32_t)g.cell_cap * cell_bytes_for(includes_run_root)) + a16((uint32_t)trace_cap * 32u) + g.heap + g.scratch;
+  g.bytes = (uint32_t)sizeof(SlabHeader) + (uint32_t)n * (uint32_t)sizeof(NodeRec) + miss_dl_bytes_for((uint32_t)n) + a16((uint32_t)g.cell_cap * cell_bytes_for(includes_run_root)) + a16((uint32_t)trace_cap * 32u) + g.heap + g.scratch;
   return g;
 }
 void place_slab(emat_backend* h, size_t p, const SlabGeo& g, uint64_t& off, uint32_t content_bytes) {

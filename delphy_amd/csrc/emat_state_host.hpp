@@ -73,7 +73,7 @@ struct PartHost {
   // is made and never again (subrun.cpp:17-26); recomputing them half way gives the same numbers up to rounding -- and a chain that can tell: a node whose
   // d log G / dt cancels exactly (every site missing below one child or the other) takes the uniform branch of the bounded exponential with the maintained
   // lambda_i and the other branch with a recomputed one that is two units in the last place off (EMAT_FUZZ_SEED=6202, case 53, found in round 6).
-  std::vector<double> kept_lambda; std::vector<int32_t> kept_n_missing; double kept_log_G = 0.0, kept_log_aug_prior = 0.0;
+  std::vector<double> kept_lambda; std::vector<int32_t> kept_n_missing; std::vector<uint64_t> kept_miss_dl; double kept_log_G = 0.0, kept_log_aug_prior = 0.0;
   bool derived_kept = false;       // set by finish_pass just before it re-materialises, consumed (and cleared) by materialize
 };
 

@@ -551,6 +551,11 @@ emat_status emat_debug_sample_history(emat_backend* h, int32_t part_id, int32_t 
  * the nodes are kept up to date by the steps, as in a move (emat_check_derived verifies them afterwards).  tests/ runs the ten
  * cases of the reference's tests/tree_editing_tests.cpp through it. */
 emat_status emat_debug_edit(emat_backend* h, int32_t part_id, int32_t X, int32_t n_ops, const int32_t* op_kind, const int32_t* op_node, const double* op_t);
+/* Every resident part's remembered missation rate changes -- one number per node, kept beside the node records and put back to "not
+ * known" by whatever writes the node's missation lists -- against a fresh evaluation on the lists as they stand: out_2n[2 p] = nodes of
+ * part p whose remembered value is known and differs from it in bits (0 unless an invalidation is missing), out_2n[2 p + 1] = nodes whose
+ * value is known.  Nothing is recalculated first. */
+emat_status emat_debug_miss_dl_check(emat_backend* h, int32_t* out_2n);
 /* The device's interval-set algebra on two valid sets given as (start, end) pairs (reference interval_set.h:130-138, 238-500):
  * op 1 merge, 2 intersect, 3 subtract -> pairs in `out` (room for na + nb + 1 pairs), *n_out = their number; op 5 contains
  * (site b[0]), 6 sets intersect -> *n_out = 0 / 1. */
