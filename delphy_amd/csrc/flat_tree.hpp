@@ -6,7 +6,9 @@
 #ifndef EMAT_FLAT_TREE_HPP_
 #define EMAT_FLAT_TREE_HPP_
 
+#include <algorithm>
 #include <cfloat>
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -41,43 +43,52 @@ struct FlatTree {
     t.assign(n, 0.0); t_min.assign(n, -FLT_MAX); t_max.assign(n, FLT_MAX);
     mut_offset.assign(n + 1, 0); miss_offset.assign(n + 1, 0); mfs_offset.assign(n + 1, 0);
   }
+  // THE enumeration of a flat tree's arrays: f(owning vector, field of the C view, which count sizes it), in the order of `emat_flat_tree`, which
+  // is also the order of the exchange format between processes (emat_run_exchange.hpp).  Everything that has to name all seventeen -- allocate,
+  // view, from_view, copy_out, the exchange format's size, writer and reader -- is written from this; a new array is added here and to the struct.
+  enum Count { kNodes, kOffsets, kMuts, kIntervals, kFromStates };
+  struct Shape {
+    int32_t nodes = 0, muts = 0, intervals = 0, from_states = 0;
+    size_t of(Count c) const { return c == kNodes ? (size_t)nodes : c == kOffsets ? (size_t)nodes + 1 : c == kMuts ? (size_t)muts : c == kIntervals ? (size_t)intervals : (size_t)from_states; }
+  };
+  template <class Tree, class F> static void for_each_array(Tree& t, F&& f) {   // Tree: FlatTree or const FlatTree
+    f(t.parent, &emat_flat_tree::parent, kNodes); f(t.child0, &emat_flat_tree::child0, kNodes); f(t.child1, &emat_flat_tree::child1, kNodes);
+    f(t.t, &emat_flat_tree::t, kNodes); f(t.t_min, &emat_flat_tree::t_min, kNodes); f(t.t_max, &emat_flat_tree::t_max, kNodes);
+    f(t.mut_offset, &emat_flat_tree::mut_offset, kOffsets); f(t.mut_site, &emat_flat_tree::mut_site, kMuts); f(t.mut_from, &emat_flat_tree::mut_from, kMuts);
+    f(t.mut_to, &emat_flat_tree::mut_to, kMuts); f(t.mut_t, &emat_flat_tree::mut_t, kMuts);
+    f(t.miss_offset, &emat_flat_tree::miss_offset, kOffsets); f(t.miss_start, &emat_flat_tree::miss_start, kIntervals); f(t.miss_end, &emat_flat_tree::miss_end, kIntervals);
+    f(t.mfs_offset, &emat_flat_tree::mfs_offset, kOffsets); f(t.mfs_site, &emat_flat_tree::mfs_site, kFromStates); f(t.mfs_state, &emat_flat_tree::mfs_state, kFromStates);
+  }
+  Shape shape() const { return Shape{num_nodes(), num_muts(), num_intervals(), num_from_states()}; }
+
   // Size every array for a download of the given shape.
   void allocate(int32_t n, int32_t nm, int32_t ni, int32_t nf) {
     resize_nodes(n);
-    mut_site.assign(nm, 0); mut_from.assign(nm, 0); mut_to.assign(nm, 0); mut_t.assign(nm, 0.0);
-    miss_start.assign(ni, 0); miss_end.assign(ni, 0);
-    mfs_site.assign(nf, 0); mfs_state.assign(nf, 0);
+    const Shape s{n, nm, ni, nf};
+    for_each_array(*this, [&](auto& vec, auto, Count c) { if (c != kNodes && c != kOffsets) vec.assign(s.of(c), 0); });
   }
   // Non-owning C view (valid while *this is alive and unmodified).
   emat_flat_tree view() {
     emat_flat_tree v;
     v.num_nodes = num_nodes(); v.root = root;
-    v.parent = parent.data(); v.child0 = child0.data(); v.child1 = child1.data();
-    v.t = t.data(); v.t_min = t_min.data(); v.t_max = t_max.data();
-    v.mut_offset = mut_offset.data(); v.mut_site = mut_site.data(); v.mut_from = mut_from.data();
-    v.mut_to = mut_to.data(); v.mut_t = mut_t.data();
-    v.miss_offset = miss_offset.data(); v.miss_start = miss_start.data(); v.miss_end = miss_end.data();
-    v.mfs_offset = mfs_offset.data(); v.mfs_site = mfs_site.data(); v.mfs_state = mfs_state.data();
+    for_each_array(*this, [&](auto& vec, auto field, Count) { v.*field = vec.data(); });
     v.cap_muts = num_muts(); v.cap_intervals = num_intervals(); v.cap_from_states = num_from_states();
     return v;
   }
   static FlatTree from_view(const emat_flat_tree& v) {
     FlatTree f;
-    int32_t n = v.num_nodes;
+    const int32_t n = v.num_nodes;
     f.root = v.root;
-    f.parent.assign(v.parent, v.parent + n); f.child0.assign(v.child0, v.child0 + n); f.child1.assign(v.child1, v.child1 + n);
-    f.t.assign(v.t, v.t + n); f.t_min.assign(v.t_min, v.t_min + n); f.t_max.assign(v.t_max, v.t_max + n);
-    f.mut_offset.assign(v.mut_offset, v.mut_offset + n + 1);
-    int32_t nm = v.mut_offset[n];
-    f.mut_site.assign(v.mut_site, v.mut_site + nm); f.mut_from.assign(v.mut_from, v.mut_from + nm);
-    f.mut_to.assign(v.mut_to, v.mut_to + nm); f.mut_t.assign(v.mut_t, v.mut_t + nm);
-    f.miss_offset.assign(v.miss_offset, v.miss_offset + n + 1);
-    int32_t ni = v.miss_offset[n];
-    f.miss_start.assign(v.miss_start, v.miss_start + ni); f.miss_end.assign(v.miss_end, v.miss_end + ni);
-    f.mfs_offset.assign(v.mfs_offset, v.mfs_offset + n + 1);
-    int32_t nf = v.mfs_offset[n];
-    f.mfs_site.assign(v.mfs_site, v.mfs_site + nf); f.mfs_state.assign(v.mfs_state, v.mfs_state + nf);
+    const Shape s{n, v.mut_offset[n], v.miss_offset[n], v.mfs_offset[n]};
+    for_each_array(f, [&](auto& vec, auto field, Count c) { vec.assign(v.*field, v.*field + s.of(c)); });
     return f;
+  }
+  // Into arrays the caller provides (a download): their capacities are checked, num_nodes and root are set.
+  emat_status copy_out(emat_flat_tree* out) const {
+    if (out->num_nodes < num_nodes() || out->cap_muts < num_muts() || out->cap_intervals < num_intervals() || out->cap_from_states < num_from_states()) return EMAT_ERR_BUFFER_TOO_SMALL;
+    out->num_nodes = num_nodes(); out->root = root;
+    for_each_array(*this, [&](const auto& vec, auto field, Count) { std::copy(vec.begin(), vec.end(), out->*field); });
+    return EMAT_OK;
   }
 };
 

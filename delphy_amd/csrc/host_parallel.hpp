@@ -134,10 +134,19 @@ struct HostSpan {
   explicit HostSpan(const char* n) : name(HostSpans::instance().on ? n : nullptr) { if (name) t0 = std::chrono::steady_clock::now(); }
   ~HostSpan() { if (name) HostSpans::instance().add(name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
 };
-struct HostLaps {   // consecutive stretches of one function: mark("name") books the time since the previous mark
-  std::chrono::steady_clock::time_point last; const bool on;
-  HostLaps() : on(HostSpans::instance().on) { if (on) last = std::chrono::steady_clock::now(); }
-  void mark(const char* name) { if (!on) return; const auto t = std::chrono::steady_clock::now(); HostSpans::instance().add(name, std::chrono::duration<double, std::milli>(t - last).count()); last = t; }
+// Consecutive stretches of one function, THE way a host function times itself: mark("name") books the time since the previous mark (or
+// skip()) under that span name (EMAT_VERBOSE=spans); lap() closes a stretch of the function's one-line progress report (any other EMAT_VERBOSE,
+// asked for with HostLaps(verbose_reports())) and ms(k) is the k-th of them, 0 when the function never got there.  Two clocks, since a report's
+// stretches and the spans cut a function at different places.  Off, either costs a branch.
+struct HostLaps {
+  using Clock = std::chrono::steady_clock;
+  Clock::time_point last, last_lap; const bool on, report; std::vector<double> laps;
+  explicit HostLaps(bool with_report = false) : on(HostSpans::instance().on), report(with_report) { if (on || report) last = last_lap = Clock::now(); }
+  static double between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+  void mark(const char* name) { if (!on) return; const auto t = Clock::now(); HostSpans::instance().add(name, between(last, t)); last = t; }
+  void skip() { if (on) last = Clock::now(); }   // what ran since the last mark is booked under no name
+  void lap() { if (!report) return; const auto t = Clock::now(); laps.push_back(between(last_lap, t)); last_lap = t; }
+  double ms(size_t k) const { return k < laps.size() ? laps[k] : 0.0; }
 };
 #define EMAT_SPAN_CAT2(a, b) a##b
 #define EMAT_SPAN_CAT(a, b) EMAT_SPAN_CAT2(a, b)

@@ -63,7 +63,7 @@ emat_status emat_run_set_num_parts(emat_run* r, int32_t num_parts);
 /* NOT in the reference: at every repartition, parts of more than `max_nodes` nodes get further cut nodes, because on the GPU a pass
  * lasts as long as the chain of its largest part, and the parts of a stencil drift apart in size while it is in use (run.cpp:87-108
  * redraws stencils every 200 cycles only).  The extra cut nodes are drawn uniformly at random among the part's inner nodes -- a rule
- * that reads nothing a pass can change, so that it leaves the sampler's stationary distribution alone (emat_run.cpp, refine_stencil).
+ * that reads nothing a pass can change, so that it leaves the sampler's stationary distribution alone (emat_run_partition.hpp, refine_stencil).
  * 0 (the DEFAULT since round 6) = off: the reference's rule exactly, so that a run that sets nothing reproduces the reference's (and the
  * oracle's) partition; -1 = three times the mean part size, at least 64 (what bench.py's `inclusive` and the posterior scripts opt into);
  * > 0 = that many nodes. */
