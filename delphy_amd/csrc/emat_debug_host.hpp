@@ -71,7 +71,7 @@ emat_status emat_debug_interval_op(emat_backend* h, int32_t op, const int32_t* a
   if (h->host_only) return no_device(h);
   if (!bind_device(h)) return fail(h, EMAT_ERR_HIP, "hipSetDevice failed");
   DevBuf<IvRec> dA, dB, dO; DevBuf<int> dn;
-  HIP_TRY(dA.upload((const IvRec*)a, (size_t)na)); HIP_TRY(dB.upload((const IvRec*)b, (size_t)(op == 5 ? 0 : nb))); HIP_TRY(dO.alloc((size_t)(na + nb + 1))); HIP_TRY(dn.alloc(1));
+  HIP_TRY(dA.upload((const IvRec*)a, (size_t)na)); HIP_TRY(dB.upload((const IvRec*)b, (size_t)(op == 5 ? 0 : nb))); HIP_TRY(dO.alloc(2 * (size_t)(na + nb + 1))); HIP_TRY(dn.alloc(1));
   hipLaunchKernelGGL(k_debug_interval_op, dim3(1), dim3(64), 0, h->stream, (int)op, dA.p, (int)na, dB.p, (int)(op == 5 ? 0 : nb), op == 5 && nb > 0 ? b[0] : 0, dO.p, dn.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -79,7 +79,7 @@ emat_status emat_debug_interval_op(emat_backend* h, int32_t op, const int32_t* a
   HIP_TRY(hipMemcpy(&cnt, dn.p, sizeof(int), hipMemcpyDeviceToHost));
   if (cnt < 0) return fail(h, EMAT_ERR_INVALID_ARGUMENT, "emat_debug_interval_op: unknown op");
   *n_out = cnt;
-  if (op <= 3 && cnt > 0) HIP_TRY(hipMemcpy(out, dO.p, (size_t)cnt * sizeof(IvRec), hipMemcpyDeviceToHost));
+  if ((op <= 3 || op == 7 || op == 8) && cnt > 0) HIP_TRY(hipMemcpy(out, dO.p, (size_t)cnt * sizeof(IvRec), hipMemcpyDeviceToHost));
   return EMAT_OK;
 }
 /* test hook (header: emat_debug_tree_query) */

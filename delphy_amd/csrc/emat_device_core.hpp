@@ -544,6 +544,49 @@ EMAT_D SVec<IvRec> iv_subtract_sc(Ctx& c, const IvRec* A, int nA, const IvRec* B
   sc_trim(c, r);
   return r;
 }
+// A - B into `diff` and A & B into `rest`, in one walk over the two lists (iv_subtract's walk, which also notes what it steps over).
+// `diff` is iv_subtract(A, B) entry for entry.  `rest` is iv_subtract(A, diff) entry for entry: inside one interval of A, every
+// maximal stretch between two consecutive pieces of `diff` -- so pieces of B that touch come out joined, while two intervals of A
+// that touch stay two.  Each needs room for nA + nB intervals (a piece of either ends where an interval of A or of B ends).
+EMAT_D void iv_split(IvRec* diff, int& ndiff, IvRec* rest, int& nrest, const IvRec* A, int nA, const IvRec* B, int nB) {
+  int od = 0, orr = 0, ia = 0, ib = 0;
+  if (nA != 0) {
+    int cs = A[0].start, ce = A[0].end, g = cs;   // g: where `diff` stopped covering the current interval of A
+    while (ia != nA) {
+      bool next = false; int ds = 0, de = 0;      // the piece of `diff` this step emits, if any (ds < de)
+      if (ib == nB) { ds = cs; de = ce; next = true; }
+      else {
+        int bs = B[ib].start, be = B[ib].end;
+        if (bs < cs) {
+          if (be <= cs) ++ib;
+          else if (be < ce) { cs = be; ++ib; }
+          else next = true;
+        } else if (bs < ce) {
+          if (cs < bs) { ds = cs; de = bs; }
+          if (be < ce) { cs = be; ++ib; }
+          else next = true;
+        } else { ds = cs; de = ce; next = true; }
+      }
+      if (ds < de) {
+        if (g < ds) { rest[orr].start = g; rest[orr].end = ds; ++orr; }
+        diff[od].start = ds; diff[od].end = de; ++od; g = de;
+      }
+      if (next) {
+        if (g < ce) { rest[orr].start = g; rest[orr].end = ce; ++orr; }
+        ++ia; if (ia != nA) { cs = A[ia].start; ce = A[ia].end; g = cs; }
+      }
+    }
+  }
+  ndiff = od; nrest = orr;
+}
+// the two as scratch vectors, each as long as what it holds (the first keeps its unused tail in the arena: a few intervals, until the move ends)
+EMAT_D void iv_split_sc(Ctx& c, SVec<IvRec>& diff, SVec<IvRec>& rest, const IvRec* A, int nA, const IvRec* B, int nB) {
+  diff = sc_vec<IvRec>(c, nA + nB + 1);
+  rest = sc_vec<IvRec>(c, nA + nB + 1);
+  if (!c.failed) iv_split(diff.p, diff.n, rest.p, rest.n, A, nA, B, nB);
+  sc_trim(c, rest);
+  diff.cap = diff.n;
+}
 EMAT_D SVec<IvRec> iv_copy_sc(Ctx& c, const IvRec* A, int nA) {
   SVec<IvRec> r = sc_vec<IvRec>(c, nA);
   if (!c.failed) { for (int i = 0; i < nA; ++i) r.p[i] = A[i]; r.n = nA; }

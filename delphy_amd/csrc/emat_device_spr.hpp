@@ -658,35 +658,45 @@ EMAT_DN void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1)
   const int S = sibling_of(c, P, X);
   const double t_X = nodes_of(c)[X].t, t_P = nodes_of(c)[P].t;
   g.S = S; g.t_P = t_P;
-  int depth = 0, path_muts = 0;
-  { EMAT_TIMED(1);   /* start_inner: walk to the part's root (depth, path_muts) */
-  for (int cur = X; cur != k_no_node; cur = nodes_of(c)[cur].parent) { ++depth; if (c.includes_run_root || nodes_of(c)[cur].parent != k_no_node) path_muts += nmuts(c, cur); } }
   // The hot path rarely climbs more than two or three branches (it ends where the sibling's missing sites are used up), while
   // the path to the part's root is 5-15 long: room for four entries to start with, doubled when they run out (the
-  // abandoned array stays in the arena until the move ends) -- 104 bytes per entry of an arena of a few KB.
-  int bi_cap = depth + 2 < 4 ? depth + 2 : 4;
+  // abandoned array stays in the arena until the move ends) -- 104 bytes per entry of an arena of a few KB.  Nothing here is sized
+  // by the path to the part's root: the climb ends at the part's root by itself, and the lists grow with what it meets.
+  int bi_cap = 4;
   EMAT_TIMED_BLOCK(1, setup_timer);   /* start_inner: setup (branch infos, PX, sliding missations, pl_A of PX) */
   g.bi = (BranchInfo*)sc_alloc(c, (uint32_t)bi_cap * (uint32_t)sizeof(BranchInfo));
   if (c.failed) return;
   auto bi_room = [&]() {
     if (g.nbi < bi_cap) return;
-    if (bi_cap >= depth + 2) { EMAT_FAIL(c, k_part_overflow); return; }
-    const int ncap = 2 * bi_cap < depth + 2 ? 2 * bi_cap : depth + 2;
+    const int ncap = 2 * bi_cap;
     BranchInfo* nb = (BranchInfo*)sc_alloc(c, (uint32_t)ncap * (uint32_t)sizeof(BranchInfo));
     if (c.failed) return;
     for (int i = 0; i < g.nbi; ++i) nb[i] = g.bi[i];
     g.bi = nb; bi_cap = ncap;
   };
+  // sliding_missations = S's missations: what [0, L) keeps of them, while PX.hot is what it loses to them -- one walk.  (A node's
+  // missations are maximal intervals inside [0, L): an uploaded tree is refused otherwise and merge, intersect and subtract keep them so.
+  // So the walk neither joins nor cuts any: sl_iv is the list entry for entry.)
+  SVec<IvRec> sl_iv;
   {
     BranchInfo& PX = g.bi[g.nbi++]; bi_init(PX);
     PX.A = P; PX.B = X; PX.is_open = false; PX.T_to_X = t_X - t_P;
     PX.warm = sc_vec<IvRec>(c, 1); { IvRec all; all.start = 0; all.end = c.L; push(c, PX.warm, all); }
-    PX.hot = iv_subtract_sc(c, PX.warm.p, PX.warm.n, miss_of(c, S), (int)nodes_of(c)[S].miss.cnt);
+    iv_split_sc(c, PX.hot, sl_iv, PX.warm.p, PX.warm.n, miss_of(c, S), (int)nodes_of(c)[S].miss.cnt);
   }
-  // sliding_missations = copy of S's missations
-  SVec<IvRec> sl_iv = iv_copy_sc(c, miss_of(c, S), (int)nodes_of(c)[S].miss.cnt);
-  SVec<FsRec> sl_fs = sc_vec<FsRec>(c, (int)nodes_of(c)[S].mfs.cnt + path_muts + 1);
-  { const FsRec* f = mfs_of(c, S); for (int i = 0; i < (int)nodes_of(c)[S].mfs.cnt; ++i) push(c, sl_fs, f[i]); }
+  // (its from-states: room for S's and for one more per mutation of the first branch above; fs_room gives more, level by level)
+  int path_muts = nmuts(c, X);   // mutations on the branches of the hot path: all that can turn out hot
+  SVec<FsRec> sl_fs;
+  { const int nf = (int)nodes_of(c)[S].mfs.cnt;
+    sl_fs = sc_vec<FsRec>(c, nf + nmuts(c, P) + 1);
+    if (!c.failed) { const FsRec* f = mfs_of(c, S); for (int i = 0; i < nf; ++i) sl_fs.p[i] = f[i]; sl_fs.n = nf; } }
+  auto fs_room = [&](int more) {
+    if (sl_fs.n + more <= sl_fs.cap) return;
+    SVec<FsRec> nv = sc_vec<FsRec>(c, 2 * sl_fs.cap > sl_fs.n + more ? 2 * sl_fs.cap : sl_fs.n + more);
+    if (c.failed) return;
+    for (int i = 0; i < sl_fs.n; ++i) nv.p[i] = sl_fs.p[i];
+    nv.n = sl_fs.n; sl_fs = nv;
+  };
   {
     BranchInfo& PX = g.bi[0];
     PX.pl_A = nodes_of(c)[X].lambda;
@@ -694,6 +704,7 @@ EMAT_DN void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1)
     for (int i = nmuts(c, X) - 1; i >= 0; --i) PX.pl_A += dq(c, m[i].site, m[i].to, m[i].from);
   }
   EMAT_TIMED_END(setup_timer);
+  if (c.failed) return;
   double next_pl_B;
   { EMAT_TIMED(1);   /* start_inner: first delta_lambda_across_missations */
   next_pl_B = -1 * delta_lambda_across_node_missations(c, S); }   // (the sliding sets still are S's own lists, entry for entry)
@@ -706,18 +717,27 @@ EMAT_DN void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1)
     BranchInfo& bi = g.bi[g.nbi++]; bi_init(bi);
     bi.A = parent; bi.B = cur; bi.is_open = false; bi.T_to_X = t_X - nodes_of(c)[parent].t;
     bi.warm = sl_iv;
-    const MutRec* mc = muts_of(c, cur);
-    for (int i = nmuts(c, cur) - 1; i >= 0; --i) {
+    const MutRec* mc = muts_of(c, cur); const int nc = nmuts(c, cur);
+    path_muts += nc;
+    fs_room(nc); if (c.failed) break;
+    // (a branch's mutations are in time order, not site order: each is looked up)
+    for (int i = nc - 1; i >= 0; --i) {
       if (iv_contains(sl_iv.p, sl_iv.n, mc[i].site)) { partial_lambda += dq(c, mc[i].site, mc[i].to, mc[i].from); fsv_set(c, sl_fs, mc[i].site, mc[i].from); }
     }
-    bi.hot = iv_subtract_sc(c, bi.warm.p, bi.warm.n, miss_of(c, sibling), (int)nodes_of(c)[sibling].miss.cnt);
-    SVec<IvRec> new_sl = iv_subtract_sc(c, bi.warm.p, bi.warm.n, bi.hot.p, bi.hot.n);
-    sl_iv = new_sl;
-    { int w = 0; for (int i = 0; i < sl_fs.n; ++i) if (iv_contains(sl_iv.p, sl_iv.n, sl_fs.p[i].site)) sl_fs.p[w++] = sl_fs.p[i]; sl_fs.n = w; }
+    // hot = warm - the sibling's missations, and the next level's sliding set = warm - hot: one walk writes both
+    iv_split_sc(c, bi.hot, sl_iv, bi.warm.p, bi.warm.n, miss_of(c, sibling), (int)nodes_of(c)[sibling].miss.cnt);
+    // the from-states that are still sliding: both lists are in site order, so one walk over the two
+    { int w = 0, k = 0;
+      for (int i = 0; i < sl_fs.n; ++i) {
+        const int l = sl_fs.p[i].site;
+        while (k < sl_iv.n && sl_iv.p[k].end <= l) ++k;
+        if (k < sl_iv.n && sl_iv.p[k].start <= l) sl_fs.p[w++] = sl_fs.p[i];
+      }
+      sl_fs.n = w; }
     next_pl_B = -1 * delta_lambda_across_missations(c, sl_iv.p, sl_iv.n, sl_fs.p, sl_fs.n);
     bi.pl_A = partial_lambda - next_pl_B;
     partial_lambda = next_pl_B;
-    c.bytes += 64 + 16 * nmuts(c, cur) + 24 * ((int)nodes_of(c)[sibling].miss.cnt + bi.warm.n);
+    c.bytes += 64 + 16 * nc + 24 * ((int)nodes_of(c)[sibling].miss.cnt + bi.warm.n);
     if (parent != hdr_of(c)->root) {
       cur = parent; parent = nodes_of(c)[cur].parent; sibling = sibling_of(c, parent, cur);
     } else {
@@ -733,7 +753,8 @@ EMAT_DN void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1)
   } }
   if (c.failed) return;
   { EMAT_TIMED(1);   /* start_inner: distribute hot mutations along the hot path */
-  // distribute hot mutations along the hot path (spr_move.cpp:700-735): gather (mutation, owner), then split by owner
+  // distribute hot mutations along the hot path (spr_move.cpp:700-735): gather (mutation, owner) and count per owner -- in the capacity its
+  // list is about to be given --, give every owner its two lists, then deal the mutations out in one pass from the back
   struct Owned { MutRec m; int owner; int pad; };
   SVec<Owned> tmp = sc_vec<Owned>(c, path_muts + 1);
   for (int i = 0; i < g.nbi; ++i) {
@@ -745,25 +766,30 @@ EMAT_DN void start_inner_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1)
         // (the hot sets of the branch infos are pairwise disjoint -- hot_j is cut out of warm_j, warm_j+1 is what is left of it -- so the first
         // owner found is the only one: the reference's loop over all j >= i pushes the mutation exactly once too)
         bool found = false;
-        for (int j = i; j < g.nbi; ++j) if (iv_contains(g.bi[j].hot.p, g.bi[j].hot.n, mb[k].site)) { Owned o; o.m = mb[k]; o.owner = j; o.pad = 0; push(c, tmp, o); found = true; break; }
+        for (int j = i; j < g.nbi; ++j) if (iv_contains(g.bi[j].hot.p, g.bi[j].hot.n, mb[k].site)) { Owned o; o.m = mb[k]; o.owner = j; o.pad = 0; push(c, tmp, o); ++g.bi[j].hot_muts.cap; found = true; break; }
         EMAT_CHECK(c, found);
       }
     }
   }
   if (tmp.n == 0) {   // no hot mutation anywhere on the path (most grafts of a sparsely mutated tree): every list is empty, nothing to allocate or scan
     for (int j = 0; j < g.nbi; ++j) { BranchInfo& bi = g.bi[j]; bi.hot_muts.p = nullptr; bi.hot_muts.n = bi.hot_muts.cap = 0; bi.hot_deltas.p = nullptr; bi.hot_deltas.n = bi.hot_deltas.cap = 0; bi.pl_X = bi.pl_A; }
-  } else
-  for (int j = 0; j < g.nbi && !c.failed; ++j) {
-    BranchInfo& bi = g.bi[j];
-    int cnt = 0; for (int k = 0; k < tmp.n; ++k) if (tmp.p[k].owner == j) ++cnt;
-    bi.hot_muts = sc_vec<MutRec>(c, cnt);
-    bi.hot_deltas = sc_vec<SdRec>(c, cnt);
-    for (int k = tmp.n - 1; k >= 0; --k) if (tmp.p[k].owner == j) push(c, bi.hot_muts, tmp.p[k].m);   // reversed encounter order
-    bi.pl_X = bi.pl_A;
-    for (int k = 0; k < bi.hot_muts.n; ++k) {
-      const MutRec& m = bi.hot_muts.p[k];
-      if (!bi.is_open) sd_push_back(c, bi.hot_deltas, m.site, m.from, m.to);
-      bi.pl_X += dq(c, m.site, m.from, m.to);
+  } else if (!c.failed) {
+    for (int j = 0; j < g.nbi; ++j) {
+      BranchInfo& bi = g.bi[j];
+      const int cnt = bi.hot_muts.cap;
+      bi.hot_muts = sc_vec<MutRec>(c, cnt);
+      bi.hot_deltas = sc_vec<SdRec>(c, cnt);
+    }
+    if (c.failed) return;
+    for (int k = tmp.n - 1; k >= 0; --k) { SVec<MutRec>& v = g.bi[tmp.p[k].owner].hot_muts; v.p[v.n++] = tmp.p[k].m; }   // reversed encounter order (v.n stays below the count taken above)
+    for (int j = 0; j < g.nbi && !c.failed; ++j) {
+      BranchInfo& bi = g.bi[j];
+      bi.pl_X = bi.pl_A;
+      for (int k = 0; k < bi.hot_muts.n; ++k) {
+        const MutRec& m = bi.hot_muts.p[k];
+        if (!bi.is_open) sd_push_back(c, bi.hot_deltas, m.site, m.from, m.to);
+        bi.pl_X += dq(c, m.site, m.from, m.to);
+      }
     }
   } }
   return;

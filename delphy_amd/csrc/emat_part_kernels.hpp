@@ -865,6 +865,12 @@ __global__ void k_debug_interval_op(int op, const IvRec* A, int nA, const IvRec*
   else if (op == 3) *n_out = dev::iv_subtract(out, A, nA, B, nB);
   else if (op == 5) *n_out = dev::iv_contains(A, nA, site) ? 1 : 0;
   else if (op == 6) *n_out = dev::iv_intersects(A, nA, B, nB) ? 1 : 0;
+  else if (op == 7 || op == 8) {   // iv_split: 7 = its difference, 8 = its remainder (`out` holds two lists of nA + nB + 1)
+    IvRec* rest = out + nA + nB + 1; int nd = 0, nr = 0;
+    dev::iv_split(out, nd, rest, nr, A, nA, B, nB);
+    if (op == 8) for (int k = 0; k < nr; ++k) out[k] = rest[k];
+    *n_out = op == 7 ? nd : nr;
+  }
   else *n_out = -1;
 }
 

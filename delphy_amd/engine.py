@@ -863,12 +863,12 @@ class EmatBackend:
         return out
 
     def debug_interval_op(self, op: int, a, b):
-        """Test hook: the device's interval-set algebra; sets as lists of [start, end)."""
+        """Test hook: the device's interval-set algebra; sets as lists of [start, end).  Ops 7 and 8: the two lists of iv_split (a - b, and what is left of a)."""
         A = np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1, 2)); Bv = np.ascontiguousarray(np.asarray(b, np.int32).reshape(-1))
         nb = Bv.shape[0] if op == 5 else Bv.shape[0] // 2
         out = np.zeros((A.shape[0] + nb + 1, 2), np.int32); n = C.c_int32(); ip = C.POINTER(C.c_int32)
         self._ck(self._lib.emat_debug_interval_op(self._h, op, A.ctypes.data_as(ip), A.shape[0], Bv.ctypes.data_as(ip), nb, out.ctypes.data_as(ip), C.byref(n)), "emat_debug_interval_op")
-        return out[: n.value].tolist() if op <= 3 else bool(n.value)
+        return out[: n.value].tolist() if op <= 3 or op in (7, 8) else bool(n.value)
 
     def debug_tree_query(self, part: int, op: int, a, b) -> np.ndarray:
         """Test hook: the moves' find_MRCA_of (op 0) / descends_from (op 1) on a resident part; -1 = no node."""

@@ -558,7 +558,8 @@ emat_status emat_debug_edit(emat_backend* h, int32_t part_id, int32_t X, int32_t
 emat_status emat_debug_miss_dl_check(emat_backend* h, int32_t* out_2n);
 /* The device's interval-set algebra on two valid sets given as (start, end) pairs (reference interval_set.h:130-138, 238-500):
  * op 1 merge, 2 intersect, 3 subtract -> pairs in `out` (room for na + nb + 1 pairs), *n_out = their number; op 5 contains
- * (site b[0]), 6 sets intersect -> *n_out = 0 / 1. */
+ * (site b[0]), 6 sets intersect -> *n_out = 0 / 1; op 7 / 8: the graft analysis's one-walk split of a by b, its difference (= op 3) /
+ * what is left of a (= a minus that difference, entry for entry) -> pairs in `out`. */
 emat_status emat_debug_interval_op(emat_backend* h, int32_t op, const int32_t* a, int32_t na, const int32_t* b, int32_t nb, int32_t* out, int32_t* n_out);
 /* How often the cut-state pools (out3[0]) and the list heaps (out3[1]) of the HBM-resident tree had to grow (with
  * EMAT_TREE_TIGHT set in the environment they start without any room, so that tests reach those paths), and how many
