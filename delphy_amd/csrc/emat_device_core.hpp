@@ -120,6 +120,7 @@ struct Ctx {
   NodeRec* N;
   // evolution model: per-site arrays in HBM, per-partition HKY tables in LDS when staged
   int L;
+  uint32_t heap_limit;        // a move starts only while hdr->heap_top <= heap_limit: fixed when the leg has set the heap's end (set_heap_limit, emat_device_moves.hpp)
   // per-site model arrays: always in HBM, typed as global pointers so that they are read with global_load (own
   // counter, no LDS-aperture check) instead of generic flat_load
   const __attribute__((address_space(1))) uint8_t* ref;
@@ -155,10 +156,13 @@ struct Ctx {
   // statistics
   int64_t bytes;
   int64_t bytes_w;            // the part of `bytes` that is written (cells, re-timed lists, region records, re-hung nodes): roofline.algorithmic_write_bytes
-  // trace of the current move
-  double tr_log_mh; float tr_kind, tr_node, tr_acc;   // (kind, node and accept flag are small integers: floats hold them exactly)
+  // trace of the current move, in its own types: the row of four doubles is only formed where a row is stored (mcmc_sub_iteration).
+  // tr_acc < 0: the move has not been noted (it returned early, or is parked) -- its row says "not accepted, log MH ratio NaN" and
+  // tr_log_mh is not read.  tr_node, tr_kind and tr_acc are one aligned 8-byte word: begin_move sets it with one store.
+  double tr_log_mh; int32_t tr_node; int16_t tr_kind, tr_acc;
   int64_t moves_left;         // moves of the current launch still to do (run_chain_loop keeps nothing in registers across a move)
-  uint64_t mv_rng_ctr;
+  uint64_t mv_rng_ctr;       // (kept by the part that holds the run's root only: no other part can reach stop_for_cells)
+  double mix_total;           // total weight of the move mix, the upper end of the draw that picks a move: fixed per leg (set_move_mix)
   // the run-wide cell arrays (SharedCells, emat_slab.hpp): absolute cell index; the root part has its own copies in its slab
   const double* sh_ktw; const double* sh_tsop; const int32_t* sh_nact;
 };
@@ -296,6 +300,13 @@ EMAT_D int poisson(Ctx& c, double lambda) {
   while (u >= F && k < 100000) { ++k; p *= lambda / k; F += p; }
   return k;
 }
+
+// ---- algorithmic bytes (roofline.algorithmic_*_bytes of bench.py --full) ----------------------------------------------------
+// The context's 64-bit totals live in LDS, and every update of them is a load, two adds and a store the compiler cannot merge with the
+// next one (the stores in between may alias the context).  A simple move and the coalescent helpers it calls therefore count into a
+// ByteCount of their own, in registers, and the move adds it to the totals once, on its way out (count_bytes).
+struct ByteCount { int all = 0, written = 0; };   // `written`: the part of `all` that is stored, not only loaded
+EMAT_DF void count_bytes(Ctx& c, const ByteCount& n) { c.bytes += n.all; if (n.written != 0) c.bytes_w += n.written; }
 
 // ---- scratch arenas (temporaries of one move) -----------------------------------------------------------
 template <class T> struct SVec { T* p; int n; int cap; };
@@ -993,7 +1004,7 @@ EMAT_DN void stop_for_cells(Ctx& c, int kind) {
   if (hdr_of(c)->status == 0) hdr_of(c)->status = k_part_need_cells;
 }
 // cpp:37-79 on k_bar_p
-EMAT_DF void coal_add_interval(Ctx& c, double t_start, double t_end, double delta_k) {
+EMAT_DF void coal_add_interval(Ctx& c, double t_start, double t_end, double delta_k, ByteCount& n) {
   if (c.failed) return;
   if (t_start < t_end) { double t = t_start; t_start = t_end; t_end = t; }
   Cells k = cells_of(c);
@@ -1009,7 +1020,7 @@ EMAT_DF void coal_add_interval(Ctx& c, double t_start, double t_end, double delt
     k.kbar_p[cell_end - first] += delta_k * (cell_ubound(c, cell_end) - t_end) / ts;
     for (int i = cell_start + 1; i < cell_end; ++i) k.kbar_p[i - first] += delta_k;
   }
-  c.bytes += 8 * (int64_t)(cell_end - cell_start + 1); c.bytes_w += 8 * (int64_t)(cell_end - cell_start + 1);
+  n.all += 8 * (cell_end - cell_start + 1); n.written += 8 * (cell_end - cell_start + 1);
 }
 EMAT_DF double coal_cell_term(const Ctx& c, const Cells& k, int w, double new_k, double old_k) {
   double na, tsop, ktw;   // num_active_parts, t_step / popsize_bar (the same double, divided when the cell was made), k_twiddle_bar
@@ -1020,7 +1031,7 @@ EMAT_DF double coal_cell_term(const Ctx& c, const Cells& k, int w, double new_k,
       - (k.ktw_p[w] * na - ktw + 0.5) * (new_k - old_k));
 }
 // cpp:388-459
-template <bool kGrow = true> EMAT_DF double coal_delta_on_add_interval(Ctx& c, double min_t, double max_t, double delta_k) { EMAT_TIMED(0);
+template <bool kGrow = true> EMAT_DF double coal_delta_on_add_interval(Ctx& c, double min_t, double max_t, double delta_k, ByteCount& n) { EMAT_TIMED(0);
   { int cm = cell_for(c, max_t); if (cm < hdr_of(c)->cell_first || cm >= hdr_of(c)->n_cells_total) { EMAT_FAIL(c, k_part_internal); return 0.0; } }
   coal_ensure_space<kGrow>(c, min_t);
   if (c.failed) return 0.0;
@@ -1043,26 +1054,29 @@ template <bool kGrow = true> EMAT_DF double coal_delta_on_add_interval(Ctx& c, d
     old_k = k.kbar_p[i - first]; new_k = old_k + delta_k * dt_end / ts;
     d -= coal_cell_term(c, k, i - first, new_k, old_k);
   }
-  c.bytes += 36 * (int64_t)(cell_end - cell_start + 1);
+  n.all += 36 * (cell_end - cell_start + 1);
   EMAT_COUNT(c, 13, cell_end - cell_start + 1); EMAT_COUNT(c, 14, 1);
   return d;
 }
-template <bool kGrow = true> EMAT_DF double coal_delta_displace_coalescence(Ctx& c, double old_t, double new_t) { EMAT_TIMED(0);   // cpp:310-326
-  double d = (old_t <= new_t) ? coal_delta_on_add_interval<kGrow>(c, old_t, new_t, -1.0) : coal_delta_on_add_interval<kGrow>(c, new_t, old_t, +1.0);
+template <bool kGrow = true> EMAT_DF double coal_delta_displace_coalescence(Ctx& c, double old_t, double new_t, ByteCount& n) { EMAT_TIMED(0);   // cpp:310-326
+  double d = (old_t <= new_t) ? coal_delta_on_add_interval<kGrow>(c, old_t, new_t, -1.0, n) : coal_delta_on_add_interval<kGrow>(c, new_t, old_t, +1.0, n);
   { EMAT_TIMED(0); d -= log_pop_ratio_uniform(c.pop, new_t, old_t); }
   return d;
 }
-template <bool kGrow = true> EMAT_DF double coal_delta_displace_tip(Ctx& c, double old_t, double new_t) {           // cpp:337-353
-  return (old_t <= new_t) ? coal_delta_on_add_interval<kGrow>(c, old_t, new_t, +1.0) : coal_delta_on_add_interval<kGrow>(c, new_t, old_t, -1.0);
+template <bool kGrow = true> EMAT_DF double coal_delta_displace_tip(Ctx& c, double old_t, double new_t, ByteCount& n) {           // cpp:337-353
+  return (old_t <= new_t) ? coal_delta_on_add_interval<kGrow>(c, old_t, new_t, +1.0, n) : coal_delta_on_add_interval<kGrow>(c, new_t, old_t, -1.0, n);
 }
-template <bool kGrow = true> EMAT_DF void coal_coalescence_displaced(Ctx& c, double old_t, double new_t) {           // cpp:301-308
+template <bool kGrow = true> EMAT_DF void coal_coalescence_displaced(Ctx& c, double old_t, double new_t, ByteCount& n) {           // cpp:301-308
   coal_ensure_space<kGrow>(c, new_t);
-  coal_add_interval(c, old_t, new_t, old_t <= new_t ? -1.0 : +1.0);
+  coal_add_interval(c, old_t, new_t, old_t <= new_t ? -1.0 : +1.0, n);
 }
-template <bool kGrow = true> EMAT_DF void coal_tip_displaced(Ctx& c, double old_t, double new_t) {                   // cpp:328-335
+template <bool kGrow = true> EMAT_DF void coal_tip_displaced(Ctx& c, double old_t, double new_t, ByteCount& n) {                   // cpp:328-335
   coal_ensure_space<kGrow>(c, new_t);
-  coal_add_interval(c, old_t, new_t, old_t <= new_t ? +1.0 : -1.0);
+  coal_add_interval(c, old_t, new_t, old_t <= new_t ? +1.0 : -1.0, n);
 }
+// The topology moves (one move in sixteen, their helpers out of line) count at every site, straight into the context.
+EMAT_DF double coal_delta_displace_coalescence(Ctx& c, double old_t, double new_t) { ByteCount n; const double d = coal_delta_displace_coalescence<true>(c, old_t, new_t, n); count_bytes(c, n); return d; }
+EMAT_DF void coal_coalescence_displaced(Ctx& c, double old_t, double new_t) { ByteCount n; coal_coalescence_displaced<true>(c, old_t, new_t, n); count_bytes(c, n); }
 
 // ---- incomplete gamma (replaces Boost gamma_q / gamma_q_inv used at spr_study.cpp:368,463,544;
 //      series / modified-Lentz continued fraction, inverse by Halley steps) --------------------------------------------

@@ -11,8 +11,12 @@ namespace EMAT_DEV_NS {
 #endif
 enum { k_inner_node_displace = 0, k_tip_displace = 1, k_branch_reform = 2, k_subtree_slide = 3, k_spr1 = 4 };
 
-EMAT_D void begin_move(Ctx& c, int kind) { hdr_of(c)->proposed[kind]++; c.tr_kind = (double)kind; c.tr_node = -1.0; c.tr_acc = 0.0; c.tr_log_mh = __builtin_nan(""); }
-EMAT_D void note_move(Ctx& c, int node, double log_mh, bool acc, int kind) { c.tr_node = (double)node; c.tr_log_mh = log_mh; c.tr_acc = acc ? 1.0 : 0.0; if (acc) hdr_of(c)->accepted[kind]++; }
+// What a move leaves for its trace row (Ctx::tr_*): begin_move says which move it is and that it has neither picked a node nor been
+// noted; the move stores the node it picked, once, right after the pick -- a move that returns early leaves the row at that --; and
+// note_move adds the verdict to it.
+EMAT_D void trace_nothing(Ctx& c, int kind) { c.tr_node = -1; c.tr_kind = (int16_t)kind; c.tr_acc = -1; }
+EMAT_D void begin_move(Ctx& c, int kind) { hdr_of(c)->proposed[kind]++; trace_nothing(c, kind); }
+EMAT_D void note_move(Ctx& c, double log_mh, bool acc, int kind) { c.tr_log_mh = log_mh; c.tr_acc = acc ? 1 : 0; if (acc) hdr_of(c)->accepted[kind]++; }
 EMAT_D bool mh_accept(Ctx& c, double log_mh) { return log_mh >= 0.0 || uniform_co(c, 0.0, 1.0) < m_exp(log_mh); }
 
 // distributions.h:38-69
@@ -48,7 +52,7 @@ EMAT_NOTAIL EMAT_DN void spr_move_core(Ctx& c, int X, int new_branch, double new
     const int P = nodes_of(c)[X].parent;
     const double new_t_P = new_t;
     if (new_t_P == t_X || new_t_P == nodes_of(c)[new_branch].t || (P != hdr_of(c)->root && new_t_P == nodes_of(c)[nodes_of(c)[P].parent].t)) return;
-    if (coal_needs_cells(c, new_t_P)) { stop_for_cells(c, (int)c.tr_kind); return; }   // before the graft is peeled: nothing has changed yet
+    if (coal_needs_cells(c, new_t_P)) { stop_for_cells(c, c.tr_kind); return; }   // before the graft is peeled: nothing has changed yet
     CoreFrame* f = (CoreFrame*)sc_alloc(c, (uint32_t)sizeof(CoreFrame));
     if (c.failed) return;
     c.frame = (uint8_t*)f;
@@ -72,7 +76,7 @@ EMAT_NOTAIL EMAT_DN void spr_move_core(Ctx& c, int X, int new_branch, double new
   }
   if (c.failed) return;
   const bool acc = mh_accept(c, EMAT_CF(c).log_mh);
-  if (c.tr_kind == (double)k_subtree_slide) note_move(c, EMAT_CF(c).X, EMAT_CF(c).log_mh, acc, k_subtree_slide);
+  if (c.tr_kind == k_subtree_slide) note_move(c, EMAT_CF(c).log_mh, acc, k_subtree_slide);
   if (acc) {
     apply_graft(c, EMAT_CF(c).new_graft);
     hdr_of(c)->log_G -= EMAT_CF(c).old_graft.delta_log_G; hdr_of(c)->log_G += EMAT_CF(c).new_graft.delta_log_G;
@@ -89,12 +93,13 @@ EMAT_NOTAIL EMAT_DN void spr_move_core(Ctx& c, int X, int new_branch, double new
 // displaced, its coalescent grid may grow, branch reforms next to the root go through spr_move_core) and kRoot = false for
 // every other part, where none of that can happen: those versions contain no root-only code, and their only calls are the
 // out-of-line transcendentals (m_log, m_exp, ...).
-template <bool kRoot> EMAT_NOTAIL EMAT_DN void inner_node_displace_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:148-232
+// Each is a body that counts its algorithmic bytes into `n`, whichever way it leaves, and a frame that adds them to the context once.
+template <bool kRoot> EMAT_DF void inner_node_displace_body(Ctx& c, ByteCount& n) {   // subrun.cpp:148-232
   begin_move(c, k_inner_node_displace);
   int node;
   { EMAT_TIMED(2);   /* inner_displace: pick an inner node */
     int guard = 0; do { node = pick_random_node(c); } while (is_tip(c, node) && guard++ < (1 << 26)); }
-  c.tr_node = (double)node;
+  c.tr_node = node;
   const int root = hdr_of(c)->root;
   if (!kRoot && node == root) return;   // node == root && !includes_run_root
   const NodeRec nd = nodes_of(c)[node];
@@ -115,14 +120,14 @@ template <bool kRoot> EMAT_NOTAIL EMAT_DN void inner_node_displace_move(Ctx& c) 
     const MutRec* m = muts_of(c, cc);
     const int nm = nmuts(c, cc);
     for (int i = 0; i < nm; ++i) t_max = t_max < m[i].t ? t_max : m[i].t;
-    c.bytes += 64 + 16 * nm + 24 * (int)nodes_of(c)[cc].miss.cnt;
+    n.all += 64 + 16 * nm + 24 * (int)nodes_of(c)[cc].miss.cnt;
   }
   { EMAT_TIMED(2);   /* inner_displace: delta_lambda_across_node_missations of both children */
   for (int k = 0; k < 2; ++k) {
     double lambda_just_below = lambda_at_node + delta_lambda_across_node_missations(c, ch[k]);
     d_logG_dt -= -lambda_just_below;
   } }
-  c.bytes += 2 * 64 + 16 * (int)nd.muts.cnt;
+  n.all += 2 * 64 + 16 * (int)nd.muts.cnt;
   const double old_t = nd.t;
   double log_alpha_ratio = 0.0, new_t = old_t;
   if (kRoot && node == root) {
@@ -142,27 +147,28 @@ template <bool kRoot> EMAT_NOTAIL EMAT_DN void inner_node_displace_move(Ctx& c) 
   if (new_t == t_min || new_t == t_max) return;
   if (kRoot) { if (coal_needs_cells(c, new_t)) { stop_for_cells(c, k_inner_node_displace); return; } }   // nothing has changed yet
   double delta_log_G = d_logG_dt * (new_t - old_t);
-  double delta_log_prior = coal_delta_displace_coalescence<kRoot>(c, old_t, new_t);
+  double delta_log_prior = coal_delta_displace_coalescence<kRoot>(c, old_t, new_t, n);
   if (c.failed) return;
   double log_mh = delta_log_G + delta_log_prior - log_alpha_ratio;
   bool acc;
   { EMAT_TIMED(2);   /* inner_displace: mh_accept + note_move */
   acc = mh_accept(c, log_mh);
-  note_move(c, node, log_mh, acc, k_inner_node_displace); }
+  note_move(c, log_mh, acc, k_inner_node_displace); }
   if (acc) {
     EMAT_TIMED(2);   /* inner_displace: accepted: coal_coalescence_displaced + updates */
-    coal_coalescence_displaced<kRoot>(c, old_t, new_t);
+    coal_coalescence_displaced<kRoot>(c, old_t, new_t, n);
     nodes_of(c)[node].t = new_t;
     hdr_of(c)->log_G += d_logG_dt * (new_t - old_t);
     hdr_of(c)->log_aug_prior += delta_log_prior;
   }
 }
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void inner_node_displace_move(Ctx& c) { EMAT_TIMED(2); ByteCount n; inner_node_displace_body<kRoot>(c, n); count_bytes(c, n); }
 
-template <bool kRoot> EMAT_NOTAIL EMAT_DN void tip_displace_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:234-285
+template <bool kRoot> EMAT_DF void tip_displace_body(Ctx& c, ByteCount& n) {   // subrun.cpp:234-285
   begin_move(c, k_tip_displace);
   int node;
   { int guard = 0; do { node = pick_random_node(c); } while (!is_tip(c, node) && guard++ < (1 << 26)); }
-  c.tr_node = (double)node;
+  c.tr_node = node;
   const NodeRec nd = nodes_of(c)[node];
   if (nd.t_min == nd.t_max) return;
   double t_min;   // std::max(a, b) = a < b ? b : a
@@ -172,23 +178,24 @@ template <bool kRoot> EMAT_NOTAIL EMAT_DN void tip_displace_move(Ctx& c) { EMAT_
   const double t_max = (double)nd.t_max;
   const double d_logG_dt = -nd.lambda;
   const double old_t = nd.t;
-  c.bytes += 2 * 64 + 16 * (int)nd.muts.cnt;
+  n.all += 2 * 64 + 16 * (int)nd.muts.cnt;
   double new_t = bounded_exponential(c, d_logG_dt, t_min, t_max);
   double log_alpha_ratio = d_logG_dt * (new_t - old_t);
   if (new_t == t_min || new_t == t_max) return;
   double delta_log_G = d_logG_dt * (new_t - old_t);
-  double delta_log_prior = coal_delta_displace_tip<kRoot>(c, old_t, new_t);
+  double delta_log_prior = coal_delta_displace_tip<kRoot>(c, old_t, new_t, n);
   if (c.failed) return;
   double log_mh = delta_log_G + delta_log_prior - log_alpha_ratio;
   bool acc = mh_accept(c, log_mh);
-  note_move(c, node, log_mh, acc, k_tip_displace);
+  note_move(c, log_mh, acc, k_tip_displace);
   if (acc) {
-    coal_tip_displaced<kRoot>(c, old_t, new_t);
+    coal_tip_displaced<kRoot>(c, old_t, new_t, n);
     nodes_of(c)[node].t = new_t;
     hdr_of(c)->log_G += d_logG_dt * (new_t - old_t);
     hdr_of(c)->log_aug_prior += delta_log_prior;
   }
 }
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void tip_displace_move(Ctx& c) { EMAT_TIMED(2); ByteCount n; tip_displace_body<kRoot>(c, n); count_bytes(c, n); }
 
 // phylo_tree.cpp:579-644; result in scratch
 EMAT_DF SVec<MutRec> randomize_branch_mutation_times(Ctx& c, int X) { EMAT_TIMED(2);
@@ -251,11 +258,11 @@ EMAT_DF ReformFactors reform_factors(Ctx& c, const MutRec* m, int n) { EMAT_TIME
   else if (need_log != 0u) { const int n32 = n < 32 ? n : 32; for (int j = 0; j < n32; ++j) if ((need_log >> j) & 1u) f.B[j] = m_log(f.B[j]); }   // entries from 32 on need none (all_logs would be set): never shift by >= 32
   return f;
 }
-template <bool kRoot> EMAT_NOTAIL EMAT_DN void branch_reform_move(Ctx& c) { EMAT_TIMED(2);   // subrun.cpp:287-320
+template <bool kRoot> EMAT_DF void branch_reform_body(Ctx& c, ByteCount& n_bytes) {   // subrun.cpp:287-320
   begin_move(c, k_branch_reform);
   if (hdr_of(c)->n_nodes < 3) return;
   const int X = pick_random_node(c);
-  c.tr_node = (double)X;
+  c.tr_node = X;
   if (X == hdr_of(c)->root) return;
   const int P = nodes_of(c)[X].parent;
   const int S = sibling_of(c, P, X);
@@ -268,9 +275,9 @@ template <bool kRoot> EMAT_NOTAIL EMAT_DN void branch_reform_move(Ctx& c) { EMAT
     // nothing to re-time (six branches in ten at C4): the reference's two branch_log_G are one and the same number, no random
     // number is drawn, and the empty list replaces itself
     const double g = -lam * (t_X - t_P), delta_log_G = g - g;
-    c.bytes += 2 * 64;
+    n_bytes.all += 2 * 64;
     const bool acc = mh_accept(c, delta_log_G);
-    note_move(c, X, delta_log_G, acc, k_branch_reform);
+    note_move(c, delta_log_G, acc, k_branch_reform);
     if (acc) hdr_of(c)->log_G += delta_log_G;
     return;
   }
@@ -281,15 +288,16 @@ template <bool kRoot> EMAT_NOTAIL EMAT_DN void branch_reform_move(Ctx& c) { EMAT
   { const MutRec* m = nm.p; for (int i = nm.n - 1; i >= 0; --i) { const int j = (int)m[i].pad; g_new -= f.A[j] * (m[i].t - t_P); g_new += f.B[j]; } }
   { const MutRec* m = muts_of(c, X); for (int i = n - 1; i >= 0; --i) { g_old -= f.A[i] * (m[i].t - t_P); g_old += f.B[i]; } }
   const double delta_log_G = g_new - g_old;
-  c.bytes += 2 * 64 + 2 * 16 * nm.n;
+  n_bytes.all += 2 * 64 + 2 * 16 * nm.n;
   double log_mh = delta_log_G;
   bool acc = mh_accept(c, log_mh);
-  note_move(c, X, log_mh, acc, k_branch_reform);
+  note_move(c, log_mh, acc, k_branch_reform);
   if (acc) {
     for (int i = 0; i < nm.n; ++i) nm.p[i].pad = 0;
-    list_assign<MutRec>(c, nodes_of(c)[X].muts, nm.p, nm.n); hdr_of(c)->log_G += delta_log_G; c.bytes += 16 * nm.n; c.bytes_w += 16 * nm.n;
+    list_assign<MutRec>(c, nodes_of(c)[X].muts, nm.p, nm.n); hdr_of(c)->log_G += delta_log_G; n_bytes.all += 16 * nm.n; n_bytes.written += 16 * nm.n;
   }
 }
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void branch_reform_move(Ctx& c) { EMAT_TIMED(2); ByteCount n; branch_reform_body<kRoot>(c, n); count_bytes(c, n); }
 
 // subrun.cpp:325-350, iterative with an explicit stack in scratch
 EMAT_DN SVec<int> enumerate_descendant_branches_straddling(Ctx& c, int P, double t, int X) {
@@ -331,7 +339,7 @@ EMAT_NOTAIL EMAT_DN void subtree_slide_move(Ctx& c) { EMAT_TIMED(2);   // subrun
   begin_move(c, k_subtree_slide);
   if (hdr_of(c)->n_nodes < 2) return;
   const int X = pick_random_node(c);
-  c.tr_node = (double)X;
+  c.tr_node = X;
   const int root = hdr_of(c)->root;
   if (X == root) return;
   const int P = nodes_of(c)[X].parent, S = sibling_of(c, P, X);
@@ -379,7 +387,7 @@ EMAT_NOTAIL EMAT_DN void spr1_move_begin(Ctx& c) { EMAT_TIMED(2);
   c.mu_prop = nodes_of(c)[root0].lambda / (c.L - nodes_of(c)[root0].n_missing);
   int X;
   { int guard = 0; do { X = pick_random_node(c); } while (hdr_of(c)->root == X && guard++ < (1 << 26)); }
-  c.tr_node = (double)X;
+  c.tr_node = X;
   if (nodes_of(c)[X].lambda == 0.0) return;
   const int P = nodes_of(c)[X].parent;
   const bool pruning_changes_root = P == hdr_of(c)->root;
@@ -470,7 +478,7 @@ EMAT_NOTAIL EMAT_DN void spr1_move_finish(Ctx& c) { EMAT_TIMED(2);
   const double log_mh = (fr.new_graft.delta_log_G - fr.new_graft.log_alpha_mut) - (fr.old_graft.delta_log_G - fr.old_graft.log_alpha_mut)
       + log_alpha_n2o - fr.log_alpha_o2n + d_prior;
   const bool acc = mh_accept(c, log_mh);
-  note_move(c, X, log_mh, acc, k_spr1);
+  note_move(c, log_mh, acc, k_spr1);
   if (acc) {
     apply_graft(c, fr.new_graft);
     hdr_of(c)->log_G -= fr.old_graft.delta_log_G; hdr_of(c)->log_G += fr.new_graft.delta_log_G;
@@ -523,9 +531,37 @@ EMAT_DN bool compact_heap(Ctx& c) {
   return true;
 }
 
+// What is fixed for a whole leg of a part's pass, worked out where the leg fills its context (run_moves_body), not before every move.
+// The heap mark up to which a move may start: a move wants `reserve` bytes free -- a quarter of the heap, at least 1 KB, at most
+// half the heap.  heap_begin and heap_end do not change during a leg, and compact_heap moves heap_top only.
+EMAT_D uint32_t heap_reserve(const Ctx& c) {
+  const uint32_t heap_size = hdr_of(c)->heap_end - hdr_of(c)->heap_begin;
+  uint32_t reserve = heap_size / 4 > 1024u ? heap_size / 4 : 1024u;
+  if (reserve > heap_size / 2) reserve = heap_size / 2;
+  return reserve;
+}
+// The move mix of subrun.cpp:98-121: inner-node displacement 7.5, tip displacement 7.5, branch reform 15, and with the topology moves
+// subtree slide 1 and SPR1 1.  The draw that picks a move runs over [0, mix_total).
+EMAT_D void begin_leg(Ctx& c) {
+  c.heap_limit = hdr_of(c)->heap_end - heap_reserve(c);
+  double total_weight = 15.0 + 15.0;
+  if (c.topology_moves_enabled) total_weight += 1.0 + 1.0;
+  c.mix_total = total_weight;
+}
+// The heap has less than the reserve free: squeeze the garbage out, and stop the part if that does not make the room.
+EMAT_DN bool make_heap_room(Ctx& c) {
+  const uint32_t reserve = heap_reserve(c), free_b = hdr_of(c)->heap_end - hdr_of(c)->heap_top;
+  if (free_b < reserve) {
+    if (!compact_heap(c) || hdr_of(c)->heap_end - hdr_of(c)->heap_top < reserve) { if (hdr_of(c)->status == 0) hdr_of(c)->status = k_part_need_space; return false; }
+  }
+  return true;
+}
+
 // Subrun::mcmc_sub_iteration (subrun.cpp:98-121).  Returns false when the part must stop.  An SPR1 move parks itself
 // twice for the wave's scan + study (c.svc != 0 on return): the next call resumes it.
-EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
+// kRoot: the part holds the run's root (Ctx::includes_run_root, fixed for the part's life).  Only that part can stop a move to have its
+// grid regrown and rewind its random stream to the move's first draw (stop_for_cells), so only it remembers where that was.
+template <bool kRoot> EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
 #ifdef EMAT_PROFILE_PHASES
   const long long _mv0 = clock64();
 #endif
@@ -533,46 +569,29 @@ EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
   else if (c.phase == 2) spr1_move_finish(c);
   else {
   // space check BEFORE the move, so that a stop leaves a consistent state
-  {
-    uint32_t heap_size = hdr_of(c)->heap_end - hdr_of(c)->heap_begin, free_b = hdr_of(c)->heap_end - hdr_of(c)->heap_top;
-    uint32_t reserve = heap_size / 4 > 1024u ? heap_size / 4 : 1024u;
-    if (reserve > heap_size / 2) reserve = heap_size / 2;
-    if (free_b < reserve) {
-      if (!compact_heap(c) || hdr_of(c)->heap_end - hdr_of(c)->heap_top < reserve) { if (hdr_of(c)->status == 0) hdr_of(c)->status = k_part_need_space; return false; }
-    }
-  }
+  if (hdr_of(c)->heap_top > c.heap_limit) { if (!make_heap_room(c)) return false; }
   sc_reset(c);
-  c.mv_rng_ctr = c.rng_ctr; c.mv_rng_had_spare = c.rng_has_spare;
-  c.tr_kind = -1.0; c.tr_node = -1.0; c.tr_acc = 0.0; c.tr_log_mh = __builtin_nan("");
-  if (c.only_displacing_inner_nodes) {
-    if (c.includes_run_root) inner_node_displace_move<true>(c);
-    else inner_node_displace_move<false>(c);
-  } else {
-    double total_weight = 15.0 + 15.0;
-    if (c.topology_moves_enabled) total_weight += 1.0 + 1.0;
-    double r = uniform_co(c, 0.0, total_weight);
-    if (r < 7.5) {
-      if (c.includes_run_root) inner_node_displace_move<true>(c);
-      else inner_node_displace_move<false>(c);
-    } else if (r < 15.0) {
-      if (c.includes_run_root) tip_displace_move<true>(c);
-      else tip_displace_move<false>(c);
-    } else if (r < 30.0) {
-      if (c.includes_run_root) branch_reform_move<true>(c);
-      else branch_reform_move<false>(c);
-    }
+  if (kRoot) { c.mv_rng_ctr = c.rng_ctr; c.mv_rng_had_spare = c.rng_has_spare; }
+  if (c.only_displacing_inner_nodes) inner_node_displace_move<kRoot>(c);
+  else {
+    double r = uniform_co(c, 0.0, c.mix_total);
+    if (r < 7.5) inner_node_displace_move<kRoot>(c);
+    else if (r < 15.0) tip_displace_move<kRoot>(c);
+    else if (r < 30.0) branch_reform_move<kRoot>(c);
     else if (c.topology_moves_enabled) { if (r < 31.0) subtree_slide_move(c); else spr1_move_begin(c); }
+    else trace_nothing(c, -1);
   }
   }
 #ifdef EMAT_PROFILE_PHASES
-  { const long long _dt = clock64() - _mv0; hdr_of(c)->phase_ticks[(c.tr_kind >= 3.0) ? 15 : 14] += _dt; if (c.tr_kind == 0.0) EMAT_COUNT(c, 10, _dt); else if (c.tr_kind == 1.0) EMAT_COUNT(c, 15, _dt); }   // (inner-node / tip displacements apart: reserved[10], [15])
+  { const long long _dt = clock64() - _mv0; hdr_of(c)->phase_ticks[(c.tr_kind >= 3) ? 15 : 14] += _dt; if (c.tr_kind == 0) EMAT_COUNT(c, 10, _dt); else if (c.tr_kind == 1) EMAT_COUNT(c, 15, _dt); }   // (inner-node / tip displacements apart: reserved[10], [15])
 #endif
   if (c.svc != 0 && !c.failed) return true;   // parked: the move is not over
   c.phase = 0; c.svc = 0;
   if (hdr_of(c)->status == k_part_need_cells) return false;   // stopped before the move changed anything (stop_for_cells): not a move
   if (hdr_of(c)->trace_len < hdr_of(c)->trace_cap) {
     double* tr = (double*)slab_at(c, hdr_of(c)->off_trace) + 4 * hdr_of(c)->trace_len;
-    tr[0] = c.tr_kind; tr[1] = c.tr_node; tr[2] = c.tr_acc; tr[3] = c.tr_log_mh;
+    const bool noted = c.tr_acc >= 0;
+    tr[0] = (double)c.tr_kind; tr[1] = (double)c.tr_node; tr[2] = noted ? (double)c.tr_acc : 0.0; tr[3] = noted ? c.tr_log_mh : __builtin_nan("");
     hdr_of(c)->trace_len++;
   }
   hdr_of(c)->moves_done++;
@@ -584,7 +603,7 @@ EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
 // whatever their caller kept in registers would be spilled and reloaded around each of them.
 // Returns with c.svc != 0 when the current move waits for the wave (the kernel serves it and calls again), else when the
 // moves are done or the part had to stop.
-EMAT_NOTAIL EMAT_DN void run_chain_loop(Ctx& c) {
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void run_chain(Ctx& c) {
   c.svc = 0;
   for (;;) {
     if (c.phase == 0) {
@@ -592,10 +611,12 @@ EMAT_NOTAIL EMAT_DN void run_chain_loop(Ctx& c) {
       if (rng_wants_fill(c)) { c.svc = 2; return; }                 // the wave computes the next stretch of the stream (rng_fill), then calls again
       c.moves_left -= 1;
     }
-    if (!mcmc_sub_iteration(c)) { c.moves_left = 0; c.phase = 0; c.svc = 0; return; }
+    if (!mcmc_sub_iteration<kRoot>(c)) { c.moves_left = 0; c.phase = 0; c.svc = 0; return; }
     if (c.svc != 0) return;
   }
 }
+// The one place that asks which kind of part this is: the loop and the three simple moves below it are compiled for each.
+EMAT_DF void run_chain_loop(Ctx& c) { if (c.includes_run_root) run_chain<true>(c); else run_chain<false>(c); }
 
 // ---- derived quantities of one part from scratch (Subrun::recalc_derived_quantities, subrun.cpp:17-26;
 //      calc_lambda_i phylo_tree_calc.cpp:420-436; calc_num_sites_missing_at_every_node :67-76;

@@ -119,7 +119,7 @@ template <class CtxT> __device__ inline void init_ctx(CtxT& c, uint8_t* slab, ui
   c.rng_key = c.H->rng_key; c.rng_ctr = c.H->rng_counter; c.rng_spare = c.H->rng_spare; c.rng_has_spare = c.H->rng_has_spare != 0; c.phase = 0; c.svc = 0; c.frame = nullptr;
   c.rng_base = c.rng_ctr - (uint64_t)k_rng_blocks;   // nothing computed ahead yet: the chain's first step asks the wave for it
   c.mu_prop = 0.0; c.sc_top = c.H->scratch_begin; c.A = nullptr; c.a_top = 0; c.a_end = 0; c.failed = false; c.bytes = 0; c.bytes_w = 0;
-  c.tr_kind = -1.0; c.tr_node = -1.0; c.tr_acc = 0.0; c.tr_log_mh = 0.0;
+  c.tr_kind = -1; c.tr_node = -1; c.tr_acc = -1; c.tr_log_mh = 0.0; c.heap_limit = 0; c.mix_total = 0.0;   // (the last two: dev::begin_leg, once the leg has set the heap's end)
 }
 __device__ inline const double* stage_tables(const KernelArgs& a, double* lds_tables, int lane) {
   if (a.evo.num_partitions > k_max_lds_partitions) return nullptr;
@@ -266,6 +266,7 @@ template <bool kSide> __device__ __forceinline__ void run_moves_body(const Kerne
         dev_lds::Ctx& c = *(dev_lds::Ctx*)(emat_lds_ctx);
         init_ctx(c, gslab, gslab, a, lds_tables, lds_hdr);
         H->heap_end = lds_heap_end;
+        dev_lds::begin_leg(c);
         // whatever the part leaves unused of the staging area (plus the optional extra arena) serves as the first-level
         // scratch arena of its moves; scratch that does not fit goes to the part's HBM scratch region as before
         const uint32_t used = (lds_heap_end + 15u) & ~15u;
@@ -275,11 +276,13 @@ template <bool kSide> __device__ __forceinline__ void run_moves_body(const Kerne
         // round 2's end these parts -- 40-60 nodes, the slowest chains of a pass -- ran every candidate scan through HBM)
         dev_mix::Ctx& c = *(dev_mix::Ctx*)(emat_lds_ctx);
         init_ctx(c, gslab, gslab, a, lds_tables, lds_hdr);
+        dev_mix::begin_leg(c);
         const uint32_t used = (gh->heap_begin + 15u) & ~15u;
         c.A = lds_slab + (used - (uint32_t)sizeof(SlabHeader)); c.a_end = area + a.lds_scratch_bytes - used;
       } else {
         dev::Ctx& c = *(dev::Ctx*)(emat_lds_ctx);
         init_ctx(c, gslab, gslab, a, tables_staged ? lds_tables : nullptr);
+        dev::begin_leg(c);
         if (area + a.lds_scratch_bytes > (uint32_t)sizeof(SlabHeader)) { c.A = lds_slab; c.a_end = area + a.lds_scratch_bytes - (uint32_t)sizeof(SlabHeader); }   // nothing of the part is staged: the whole dynamic block is arena
       }
       // (a later ticket of a part whose earlier one had to stop does nothing: the host gives the part more room and the rest of its moves)
