@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "emat_slab.hpp"
+#include "emat_reform_pure.hpp"
 
 #ifndef EMAT_DEVICE_COMMON_ONCE_
 #define EMAT_DEVICE_COMMON_ONCE_
@@ -459,7 +460,7 @@ EMAT_D int sibling_of(Ctx& c, int parent, int x) {
   return x == nodes_of(c)[parent].child0 ? nodes_of(c)[parent].child1 : nodes_of(c)[parent].child0;
 }
 EMAT_D MutRec make_mut(uint8_t from, int site, uint8_t to, double t) { MutRec m; m.t = t; m.site = site; m.from = from; m.to = to; m.pad = 0; return m; }
-EMAT_D bool mut_less(const MutRec& a, const MutRec& b) { return a.t < b.t || (a.t == b.t && a.site < b.site); }   // mutations.h:41-43
+EMAT_D bool mut_less(const MutRec& a, const MutRec& b) { return mut_before(a, b); }   // mutations.h:41-43 (emat_reform_pure.hpp: one spelling for the device and the host check)
 // stable insertion sort by (t, site): lists are tiny and nearly sorted
 EMAT_D void sort_muts(MutRec* p, int n) {
   for (int i = 1; i < n; ++i) { MutRec x = p[i]; int j = i - 1; while (j >= 0 && mut_less(x, p[j])) { p[j + 1] = p[j]; --j; } p[j + 1] = x; }

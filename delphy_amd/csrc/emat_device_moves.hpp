@@ -234,6 +234,17 @@ EMAT_DF SVec<MutRec> randomize_branch_mutation_times(Ctx& c, int X) { EMAT_TIMED
 // and one logarithm per mutation and list, in sequence), and each sum then runs in its own order over the same operands -- bit
 // for bit the reference's two numbers.  A re-timed mutation carries the index of the one it came from in its `pad` field.
 struct ReformFactors { double* A; double* B; };
+// The two factors of one mutation from -> to at a site of partition `pa` and relative rate `nu` (site_part, site_nu): the only spelling
+// of these expressions, for reform_factors and branch_reform_small alike.  True when B holds the ARGUMENT of its logarithm and the caller
+// still has to take m_log of it (reform_factors takes its logarithms after all loads); false when B came from the staged table.
+EMAT_DF bool mut_factors(const Ctx& c, int pa, double nu, int from, int to, double& A, double& B) {
+  const double mn = mu_of(c)[pa] * nu;
+  const double* q = q_of(c) + pa * 16;
+  A = mn * (-q[from * 5] - -q[to * 5]);      // mu nu (q_a(from) - q_a(to)), q_a = -q_aa
+  if (c.have_logq && nu == 1.0) { B = emat_lds_logq[pa * 16 + from * 4 + to]; return false; }
+  B = mn * q[from * 4 + to];
+  return true;
+}
 EMAT_DF ReformFactors reform_factors(Ctx& c, const MutRec* m, int n) { EMAT_TIMED(2);
   ReformFactors f; f.A = (double*)sc_alloc(c, (uint32_t)n * 16u); f.B = f.A + n;
   if (c.failed) return f;
@@ -247,17 +258,62 @@ EMAT_DF ReformFactors reform_factors(Ctx& c, const MutRec* m, int n) { EMAT_TIME
 #pragma unroll
     for (int k = 0; k < 4; ++k) if (j0 + k < n) {
       const MutRec& mm = m[j0 + k];
-      const double mn = mu_of(c)[pa[k]] * nu[k];
-      const double* q = q_of(c) + pa[k] * 16;
-      f.A[j0 + k] = mn * (-q[(int)mm.from * 5] - -q[(int)mm.to * 5]);      // mu nu (q_a(from) - q_a(to)), q_a = -q_aa
-      if (c.have_logq && nu[k] == 1.0) f.B[j0 + k] = emat_lds_logq[pa[k] * 16 + (int)mm.from * 4 + (int)mm.to];
-      else { f.B[j0 + k] = mn * q[(int)mm.from * 4 + (int)mm.to]; need_log |= 1u << ((j0 + k) & 31); if (j0 + k >= 32) all_logs = true; }   // the logarithm's argument; taken below
+      if (mut_factors(c, pa[k], nu[k], (int)mm.from, (int)mm.to, f.A[j0 + k], f.B[j0 + k])) { need_log |= 1u << ((j0 + k) & 31); if (j0 + k >= 32) all_logs = true; }   // the logarithm is taken below
     }
   }
   if (all_logs) { for (int j = 0; j < n; ++j) if (!(c.have_logq && site_nu(c, m[j].site) == 1.0)) f.B[j] = m_log(f.B[j]); }
   else if (need_log != 0u) { const int n32 = n < 32 ? n : 32; for (int j = 0; j < n32; ++j) if ((need_log >> j) & 1u) f.B[j] = m_log(f.B[j]); }   // entries from 32 on need none (all_logs would be set): never shift by >= 32
   return f;
 }
+// A branch reform of N = 1..4 mutations at N different sites, in registers: what reform_factors, randomize_branch_mutation_times and
+// branch_reform_body's two loops do for such a branch -- the same factors (mut_factors), the same draws at the same stream positions
+// in index order, the same stable insertion sort (sort_muts_small), the same two sums over the same operands in the same order
+// (reform_delta_small), the same verdict -- without the arena, an SVec or a pointer that may lead to LDS or to HBM: the old records
+// are read once, 16 bytes each, and an accepted move stores the N new ones over them (the list's count and capacity stay; the heap,
+// its top mark and the node's remembered rate change are not touched).  Out of line, so that the frame of branch_reform_move, which
+// three reforms in four leave through the n == 0 path, pays nothing for it.
+// Returns the bytes an accepted move stored (16 N, else 0) -- or -1, with nothing drawn and nothing changed, when two of the mutations
+// share a site: the caller then takes the general path, as it does for every longer list.
+// One difference, in a case no run reaches: the general path stops the part with k_part_overflow when neither the arena nor the part's
+// scratch region can hold 48 n bytes; this path needs no such room and goes on.
+template <int N> EMAT_DN int branch_reform_small(Ctx& c, int X, double lam, double t_X, double t_P) { EMAT_TIMED(2);
+  static_assert(N >= 1 && N <= 4, "the pairwise site test and the unrolled sort are meant for short lists");
+  MutRec* const list = (MutRec*)__builtin_assume_aligned(muts_of(c, X), 16);   // heap_alloc hands out multiples of 16 bytes
+  ReformMut old[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) __builtin_memcpy(&old[i].m, list + i, 16);
+  bool twice = false;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int j = i + 1; j < N; ++j) twice = twice || old[i].m.site == old[j].m.site;
+  }
+  if (twice) return -1;
+  int pa[N]; double nu[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { pa[i] = site_part(c, old[i].m.site); nu[i] = site_nu(c, old[i].m.site); }   // all loads in flight together
+  bool need_log[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) need_log[i] = mut_factors(c, pa[i], nu[i], (int)old[i].m.from, (int)old[i].m.to, old[i].A, old[i].B);
+#pragma unroll
+  for (int i = 0; i < N; ++i) if (need_log[i]) old[i].B = m_log(old[i].B);
+  ReformMut nw[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { nw[i] = old[i]; nw[i].m.t = uniform_oc(c, t_P, t_X); nw[i].m.pad = (uint16_t)i; }   // pad: where it came from, as on the general path
+  sort_muts_small<N>(nw);
+  const double delta_log_G = reform_delta_small<N>(old, nw, lam, t_X, t_P);
+  const bool acc = mh_accept(c, delta_log_G);
+  note_move(c, delta_log_G, acc, k_branch_reform);
+  if (!acc) return 0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) { nw[i].m.pad = 0; __builtin_memcpy(list + i, &nw[i].m, 16); }
+  hdr_of(c)->log_G += delta_log_G;
+  return 16 * N;
+}
+// The longest list branch_reform_small is built for (0: every list with mutations takes the general path).
+#ifndef EMAT_REFORM_SMALL_MAX
+#define EMAT_REFORM_SMALL_MAX 4
+#endif
 template <bool kRoot> EMAT_DF void branch_reform_body(Ctx& c, ByteCount& n_bytes) {   // subrun.cpp:287-320
   begin_move(c, k_branch_reform);
   if (hdr_of(c)->n_nodes < 3) return;
@@ -272,7 +328,7 @@ template <bool kRoot> EMAT_DF void branch_reform_body(Ctx& c, ByteCount& n_bytes
   const double lam = nodes_of(c)[X].lambda;
   const int n = nmuts(c, X);
   if (n == 0) {
-    // nothing to re-time (six branches in ten at C4): the reference's two branch_log_G are one and the same number, no random
+    // nothing to re-time (three branches in four at C4): the reference's two branch_log_G are one and the same number, no random
     // number is drawn, and the empty list replaces itself
     const double g = -lam * (t_X - t_P), delta_log_G = g - g;
     n_bytes.all += 2 * 64;
@@ -281,6 +337,27 @@ template <bool kRoot> EMAT_DF void branch_reform_body(Ctx& c, ByteCount& n_bytes
     if (acc) hdr_of(c)->log_G += delta_log_G;
     return;
   }
+  if (n <= EMAT_REFORM_SMALL_MAX) {
+    // of the branches with mutations at C4, 55 % carry one, 76 % at most two, 91.5 % at most four, none of them a site twice
+    int stored = -1;
+    switch (n) {
+#if EMAT_REFORM_SMALL_MAX >= 1
+      case 1: stored = branch_reform_small<1>(c, X, lam, t_X, t_P); break;
+#endif
+#if EMAT_REFORM_SMALL_MAX >= 2
+      case 2: stored = branch_reform_small<2>(c, X, lam, t_X, t_P); break;
+#endif
+#if EMAT_REFORM_SMALL_MAX >= 3
+      case 3: stored = branch_reform_small<3>(c, X, lam, t_X, t_P); break;
+#endif
+#if EMAT_REFORM_SMALL_MAX >= 4
+      case 4: stored = branch_reform_small<4>(c, X, lam, t_X, t_P); break;
+#endif
+      default: break;
+    }
+    if (stored >= 0) { n_bytes.all += 2 * 64 + 2 * 16 * n + stored; n_bytes.written += stored; return; }
+  }
+  // five mutations or more, or a site twice on the branch
   const ReformFactors f = reform_factors(c, muts_of(c, X), n);
   SVec<MutRec> nm = randomize_branch_mutation_times(c, X);
   if (c.failed) return;
