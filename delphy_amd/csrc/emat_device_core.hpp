@@ -26,6 +26,7 @@
 
 #include "emat_slab.hpp"
 #include "emat_reform_pure.hpp"
+#include "emat_rng_pos.hpp"
 
 #ifndef EMAT_DEVICE_COMMON_ONCE_
 #define EMAT_DEVICE_COMMON_ONCE_
@@ -43,6 +44,8 @@ constexpr uint32_t k_lds_ctx_bytes = 288;
 // k_rng_blocks counters side by side (one block, two 64-bit draws, per lane) into this array, and the chain's draws become a 16-byte LDS
 // read instead of ten rounds of 32 x 32 -> 64 multiplies on the scalar unit (a third of a simple move's scalar instructions; inlined
 // at every draw, also a good part of the code the instruction cache has to hold).  Same counters, same numbers, same order.
+// The blocks lie in the array as consecutive 64-bit words in draw order (x | y << 32, then z | w << 32), so the chain's place in the
+// stream is one index into it (Ctx::rng_pos, emat_rng_pos.hpp) and a draw is an 8-byte read.
 // 0 switches it off (every draw computes its block).
 #ifndef EMAT_RNG_BLOCKS
 #define EMAT_RNG_BLOCKS 32
@@ -138,14 +141,16 @@ struct Ctx {
   bool includes_run_root;
   bool uniform_sites;         // one site partition and nu_l == 1 everywhere (EvoTable::uniform_sites): site_part / site_nu answer without a load
   bool have_logq;             // emat_lds_logq is filled (the HKY tables are staged): sites of relative rate 1 take their log(mu q_ab) from it
-  bool rng_has_spare;         // rng_spare holds the second 64-bit half of the last Philox block, not yet consumed
   // A move that wants work done by the whole wave (candidate scan and study of an SPR move) parks itself: `phase` says
   // where it resumes, `svc` what the wave is to do meanwhile, `frame` points at the move's state in the scratch arena.
   uint8_t phase, svc;
-  // RNG (Philox4x32-10; one 128-bit block per draw)
-  uint64_t rng_key, rng_ctr;
+  // RNG (Philox4x32-10; one 128-bit block per two draws).  The next draw is 64-bit word 2 * rng_base + rng_pos of the stream
+  // (emat_rng_pos.hpp): word rng_pos of emat_lds_rng while rng_pos < 2 * k_rng_blocks, computed by the draw itself beyond.
+  uint64_t rng_key;
+  uint32_t rng_pos;
+  uint32_t mv_rng_pos;        // rng_pos at the first draw of the current move, see stop_for_cells (kept by the part that holds the run's root only: no other part can get there)
   uint64_t rng_base;          // emat_lds_rng holds the blocks of counters rng_base .. rng_base + k_rng_blocks - 1 (rng_fill)
-  uint64_t rng_spare;
+  uint64_t rng_spare;         // beyond the buffer: the second word of the block that word rng_pos - 1 or rng_pos belongs to (rng_next64_computed)
   uint8_t* frame;
   double mu_prop;             // effective JC69 rate of the current SPR move (subrun.cpp:502,710)
   // scratch: a small LDS arena first (A), the part's HBM scratch region as overflow (offsets from G)
@@ -153,7 +158,6 @@ struct Ctx {
   uint32_t a_top, a_end;      // byte offsets from A
   uint32_t sc_top;            // HBM arena bump pointer (byte offset from G)
   bool failed;
-  bool mv_rng_had_spare;      // RNG position at the first draw of the current move: (mv_rng_ctr, mv_rng_had_spare), see stop_for_cells
   // statistics
   int64_t bytes;
   int64_t bytes_w;            // the part of `bytes` that is written (cells, re-timed lists, region records, re-hung nodes): roofline.algorithmic_write_bytes
@@ -162,7 +166,6 @@ struct Ctx {
   // tr_log_mh is not read.  tr_node, tr_kind and tr_acc are one aligned 8-byte word: begin_move sets it with one store.
   double tr_log_mh; int32_t tr_node; int16_t tr_kind, tr_acc;
   int64_t moves_left;         // moves of the current launch still to do (run_chain_loop keeps nothing in registers across a move)
-  uint64_t mv_rng_ctr;       // (kept by the part that holds the run's root only: no other part can reach stop_for_cells)
   double mix_total;           // total weight of the move mix, the upper end of the draw that picks a move: fixed per leg (set_move_mix)
   // the run-wide cell arrays (SharedCells, emat_slab.hpp): absolute cell index; the root part has its own copies in its slab
   const double* sh_ktw; const double* sh_tsop; const int32_t* sh_nact;
@@ -241,42 +244,60 @@ EMAT_D void philox4x32_10(uint64_t ctr, uint64_t key, uint32_t out[4]) {
   }
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
-// (out of line: the rare draw beyond what the wave has computed ahead -- a long mutational history -- and builds without the buffer)
+// (out of line: the rare draw beyond what the wave has computed ahead -- a long mutational history --, every draw on a context nobody
+// fills (the debug kernels' private one) and builds without the buffer.)  An even position opens the block of counter
+// rng_base + (rng_pos >> 1), returns its first word and keeps the second in rng_spare; an odd one returns rng_spare -- the word before it
+// came through here, or the spare came from the slab header when the leg began: Philox runs once per block.
+constexpr uint32_t k_rng_fold_at = 1u << 30;    // far beyond what one move can draw (rng_rewind_to_move_start relies on rng_base staying put within a move)
 EMAT_DN uint64_t rng_next64_computed(Ctx& c) {
+  const RngPos at = rng_pos_folded(c.rng_base, c.rng_pos, k_rng_blocks, k_rng_fold_at);
+  if (at.pos != c.rng_pos) c.rng_base = at.base;
+  c.rng_pos = at.pos + 1u;
+  if (at.pos & 1u) return c.rng_spare;
   uint32_t w[4];
-  philox4x32_10(c.rng_ctr++, c.rng_key, w);
-  c.rng_spare = (uint64_t)w[2] | ((uint64_t)w[3] << 32); c.rng_has_spare = true;
+  philox4x32_10(rng_pos_block(at.base, at.pos), c.rng_key, w);
+  c.rng_spare = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
   return (uint64_t)w[0] | ((uint64_t)w[1] << 32);
 }
+EMAT_DF uint64_t rng_buffer_word(uint32_t i) { return ((const uint64_t*)emat_lds_rng)[i]; }
 EMAT_D uint64_t rng_next64(Ctx& c) {
-  if (c.rng_has_spare) { c.rng_has_spare = false; return c.rng_spare; }
-  if (k_rng_blocks != 0) {
-    const uint64_t k = c.rng_ctr - c.rng_base;
-    if (k < (uint64_t)k_rng_blocks) {
-      const uint4 w = *(const uint4*)&emat_lds_rng[(uint32_t)k * 4u];
-      c.rng_ctr += 1;
-      c.rng_spare = (uint64_t)w.z | ((uint64_t)w.w << 32); c.rng_has_spare = true;
-      return (uint64_t)w.x | ((uint64_t)w.y << 32);
-    }
-  }
+  const uint32_t pos = c.rng_pos;
+  if (rng_pos_in_buffer(pos, k_rng_blocks)) { c.rng_pos = pos + 1u; return rng_buffer_word(pos); }
   return rng_next64_computed(c);
 }
-// All lanes: the blocks of the next k_rng_blocks counters (the caller synchronises the wave before and after).
+// All lanes: the k_rng_blocks blocks from the one that holds the next word (the caller synchronises the wave before and after).
+// Every lane reads position and base, and lane 0 the word it keeps, before any lane writes: the workgroup is ONE wave, whose LDS
+// accesses happen in program order, so the reads above the stores see the old values in every lane.
 EMAT_D void rng_fill(Ctx& c, int lane) {
   if (k_rng_blocks == 0) return;
-  const uint64_t base = c.rng_ctr;
-  if (lane < (int)k_rng_blocks) { uint32_t w[4]; philox4x32_10(base + (uint64_t)lane, c.rng_key, w); *(uint4*)&emat_lds_rng[(uint32_t)lane * 4u] = make_uint4(w[0], w[1], w[2], w[3]); }
-  if (lane == 0) c.rng_base = base;
+  const uint32_t pos = c.rng_pos;
+  const RngPos to = rng_pos_after_fill(c.rng_base, pos);
+  // the second word of the last block opened leaves the buffer with this fill: the slab header wants it if the leg ends before the next draw
+  if (lane == 0 && (pos & 1u) == 0 && rng_pos_in_buffer(rng_pos_spare_word(pos), k_rng_blocks)) c.rng_spare = rng_buffer_word(rng_pos_spare_word(pos));
+  if (lane < (int)k_rng_blocks) { uint32_t w[4]; philox4x32_10(to.base + (uint64_t)lane, c.rng_key, w); *(uint4*)&emat_lds_rng[(uint32_t)lane * 4u] = make_uint4(w[0], w[1], w[2], w[3]); }
+  if (lane == 0) { c.rng_base = to.base; c.rng_pos = to.pos; }
 }
-// the chain, between two moves: few enough blocks left that the next move might run out
+// the chain, between two moves: few enough blocks left that the next move might run out (the rule: rng_pos_wants_fill)
 #ifndef EMAT_RNG_MARGIN
 #define EMAT_RNG_MARGIN 8     // blocks (two draws each) a move may use before it has to compute its own
 #endif
-EMAT_D bool rng_wants_fill(const Ctx& c) { return k_rng_blocks != 0 && c.rng_ctr - c.rng_base + (uint64_t)EMAT_RNG_MARGIN > (uint64_t)k_rng_blocks; }
-// Rewind the stream to where the current move drew its first number (the spare half-block is recomputed, not stored).
-EMAT_DN void rng_rewind_to_move_start(Ctx& c) {
-  c.rng_ctr = c.mv_rng_ctr; c.rng_has_spare = c.mv_rng_had_spare;
-  if (c.rng_has_spare) { uint32_t w[4]; philox4x32_10(c.rng_ctr - 1, c.rng_key, w); c.rng_spare = (uint64_t)w[2] | ((uint64_t)w[3] << 32); }
+EMAT_D bool rng_wants_fill(const Ctx& c) { return rng_pos_wants_fill(c.rng_pos, k_rng_blocks, (uint32_t)EMAT_RNG_MARGIN); }
+// Rewind the stream to where the current move drew its first number.  No fill falls inside a move (run_chain asks between moves only),
+// so rng_base is what it was then; a position beyond the buffer whose block is half used gets that block's second word back.
+EMAT_D void rng_rewind_to_move_start(Ctx& c) {
+  const uint32_t pos = c.mv_rng_pos;
+  c.rng_pos = pos;
+  if ((pos & 1u) != 0 && !rng_pos_in_buffer(pos, k_rng_blocks)) { uint32_t w[4]; philox4x32_10(rng_pos_block(c.rng_base, pos), c.rng_key, w); c.rng_spare = (uint64_t)w[2] | ((uint64_t)w[3] << 32); }
+}
+// Where a leg begins and ends: the slab header keeps (rng_counter, rng_spare, rng_has_spare), the context the cursor.
+EMAT_D void rng_enter_leg(Ctx& c, const SlabHeader& h) {
+  const RngPos at = rng_pos_enter(h.rng_counter, h.rng_has_spare, k_rng_blocks);
+  c.rng_key = h.rng_key; c.rng_base = at.base; c.rng_pos = at.pos; c.mv_rng_pos = at.pos; c.rng_spare = h.rng_spare;
+}
+EMAT_D void rng_leave_leg(const Ctx& c, SlabHeader& h) {
+  const uint32_t pos = c.rng_pos, sw = rng_pos_spare_word(pos);
+  h.rng_counter = rng_pos_counter(c.rng_base, pos); h.rng_has_spare = rng_pos_has_spare(pos);
+  h.rng_spare = rng_pos_in_buffer(sw, k_rng_blocks) ? rng_buffer_word(sw) : c.rng_spare;
 }
 EMAT_D double to_co(uint64_t a) { return (double)(a >> 11) * 0x1.0p-53; }
 EMAT_D double to_oo(uint64_t a) { return ((double)(a >> 12) + 0.5) * 0x1.0p-52; }

@@ -648,7 +648,7 @@ template <bool kRoot> EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
   // space check BEFORE the move, so that a stop leaves a consistent state
   if (hdr_of(c)->heap_top > c.heap_limit) { if (!make_heap_room(c)) return false; }
   sc_reset(c);
-  if (kRoot) { c.mv_rng_ctr = c.rng_ctr; c.mv_rng_had_spare = c.rng_has_spare; }
+  if (kRoot) c.mv_rng_pos = c.rng_pos;
   if (c.only_displacing_inner_nodes) inner_node_displace_move<kRoot>(c);
   else {
     double r = uniform_co(c, 0.0, c.mix_total);

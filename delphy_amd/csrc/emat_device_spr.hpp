@@ -540,7 +540,7 @@ EMAT_DN void start_rooty_graft_analysis(Ctx& c, int X, Graft& g) { EMAT_TIMED(1)
   return;
 }
 EMAT_D void filter_not_hot(SVec<MutRec>& v, const SVec<IvRec>& hot) { int w = 0; for (int i = 0; i < v.n; ++i) if (iv_contains(hot.p, hot.n, v.p[i].site)) v.p[w++] = v.p[i]; v.n = w; }
-EMAT_D SVec<MutRec> sample_history_for(Ctx& c, const BranchInfo& bi) {
+EMAT_DN SVec<MutRec> sample_history_for(Ctx& c, const BranchInfo& bi) {   // (a call, as before the draws became one index: LLVM would now inline it and take propose_new_graft out of line instead)
   return bi.is_open ? sample_unconstrained_mutational_history(c, c.L, bi.T_to_X, c.mu_prop)
                     : sample_mutational_history(c, c.L, bi.T_to_X, c.mu_prop, bi.hot_deltas);
 }

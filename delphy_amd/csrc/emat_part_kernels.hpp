@@ -116,8 +116,8 @@ template <class CtxT> __device__ inline void init_ctx(CtxT& c, uint8_t* slab, ui
   c.only_displacing_inner_nodes = a.flags.only_displacing_inner_nodes != 0;
   c.topology_moves_enabled = a.flags.topology_moves_enabled != 0;
   c.includes_run_root = (c.H->flags & k_flag_includes_run_root) != 0;
-  c.rng_key = c.H->rng_key; c.rng_ctr = c.H->rng_counter; c.rng_spare = c.H->rng_spare; c.rng_has_spare = c.H->rng_has_spare != 0; c.phase = 0; c.svc = 0; c.frame = nullptr;
-  c.rng_base = c.rng_ctr - (uint64_t)k_rng_blocks;   // nothing computed ahead yet: the chain's first step asks the wave for it
+  rng_enter_leg(c, *c.H);   // (nothing computed ahead yet: the chain's first step asks the wave for it)
+  c.phase = 0; c.svc = 0; c.frame = nullptr;
   c.mu_prop = 0.0; c.sc_top = c.H->scratch_begin; c.A = nullptr; c.a_top = 0; c.a_end = 0; c.failed = false; c.bytes = 0; c.bytes_w = 0;
   c.tr_kind = -1; c.tr_node = -1; c.tr_acc = -1; c.tr_log_mh = 0.0; c.heap_limit = 0; c.mix_total = 0.0;   // (the last two: dev::begin_leg, once the leg has set the heap's end)
 }
@@ -312,7 +312,7 @@ template <bool kSide> __device__ __forceinline__ void run_moves_body(const Kerne
     if (lane == 0) {
       if (raise_prio) __builtin_amdgcn_s_setprio(0);
       const dev::Ctx& c = *(const dev::Ctx*)(emat_lds_ctx);
-      H->rng_counter = c.rng_ctr; H->rng_spare = c.rng_spare; H->rng_has_spare = c.rng_has_spare ? 1u : 0u;
+      dev::rng_leave_leg(c, *H);
       H->alg_bytes += c.bytes; H->alg_write16 += (uint32_t)((c.bytes_w + 8) >> 4);
       const int64_t dt = (int64_t)(wall_clock64() - tick0);
       H->device_ticks += dt;
@@ -647,7 +647,7 @@ __global__ void __launch_bounds__(k_wave) EMAT_OCCUPANCY k_debug_graft(KernelArg
       if (!c.failed) { c.H->log_G -= g[0].delta_log_G; c.H->log_G += g[1].delta_log_G; }
     }
   }
-  c.H->rng_counter = c.rng_ctr; c.H->rng_spare = c.rng_spare; c.H->rng_has_spare = c.rng_has_spare ? 1u : 0u;
+  dev::rng_leave_leg(c, *c.H);
   out[0] = (double)(c.failed ? (c.H->status != 0 ? c.H->status : k_part_internal) : 0);
   *out_len = o.n;
 }
@@ -677,7 +677,7 @@ __global__ void __launch_bounds__(k_wave) EMAT_OCCUPANCY k_debug_sample_history(
     counts[i] = h.n;
     for (int k = 0; k < h.n; ++k, ++written) if (written < muts_cap) { double* o = muts + 4 * (size_t)written; o[0] = (double)h.p[k].site; o[1] = (double)h.p[k].from; o[2] = (double)h.p[k].to; o[3] = h.p[k].t; }
   }
-  c.H->rng_counter = c.rng_ctr; c.H->rng_spare = c.rng_spare; c.H->rng_has_spare = c.rng_has_spare ? 1u : 0u;
+  dev::rng_leave_leg(c, *c.H);
   status[0] = c.failed ? (c.H->status != 0 ? c.H->status : k_part_internal) : 0;
   status[1] = written;
 }
