@@ -33,8 +33,30 @@ emat_status mcc_store_alloc(emat_backend* h, const std::string& w, int64_t capac
     if (st) return st;
     HIP_TRY(X.parent.alloc(nodes)); HIP_TRY(X.c0.alloc(nodes)); HIP_TRY(X.c1.alloc(nodes)); HIP_TRY(X.t.alloc(nodes)); HIP_TRY(X.root.alloc((size_t)capacity));
   }
-  X.capacity = (int32_t)capacity; X.n = n; X.count = 0; X.derived_M = 0; X.is_tip.clear();
+  if (X.mut_capacity > 0 && (X.mut_slots != (int32_t)capacity || X.mut_n != n)) { HIP_TRY(hipStreamSynchronize(h->stream)); X.release_mutations(); }   // (made for other slots: emat_tree_samples_reserve_mutations again)
+  X.capacity = (int32_t)capacity; X.n = n; X.count = 0; X.derived_M = 0; X.is_tip.clear(); X.mut_used = 0;
   return EMAT_OK;
+}
+
+MccMuts mcc_muts_dev(MccHost& X) { MccMuts Mu{}; Mu.hdr = X.mut_hdr.p; Mu.ref = X.mut_ref.p; Mu.arena = X.mut_arena.p; Mu.L = X.mut_L; return Mu; }
+
+// What a push on a store with mutation room checks before it writes anything: the store's number of sites, and `records` free in the arena.
+emat_status mcc_mut_room_for(emat_backend* h, const std::string& w, int64_t records) {
+  const MccHost& X = h->mcc;
+  if (X.mut_L != h->L)
+    return fail(h, EMAT_ERR_STATE, w + ": the store keeps mutations of " + std::to_string(X.mut_L) + " sites and the handle has " + std::to_string(h->L) + ": emat_tree_samples_clear and emat_tree_samples_reserve_mutations first (site counts are never mixed)");
+  if (records > X.mut_capacity - X.mut_used)
+    return fail(h, EMAT_ERR_CAPACITY, w + ": this sample has " + std::to_string(records) + " mutation records and the arena has " + std::to_string(X.mut_capacity - X.mut_used) + " free of " + std::to_string(X.mut_capacity) +
+                                      ": nothing is pushed; emat_tree_samples_clear, or emat_tree_samples_reserve_mutations with more");
+  return EMAT_OK;
+}
+// Hands slot `slot` its segment of `records` records (-1: the sample comes without mutations); returns where it starts.
+int64_t mcc_mut_take(MccHost& X, int32_t slot, int64_t records) {
+  if (X.mut_base.size() < (size_t)X.capacity) { X.mut_base.resize((size_t)X.capacity, -1); X.mut_len.resize((size_t)X.capacity, 0); }
+  if (records < 0) { X.mut_base[(size_t)slot] = -1; X.mut_len[(size_t)slot] = 0; return -1; }
+  const int64_t base = X.mut_used;
+  X.mut_base[(size_t)slot] = base; X.mut_len[(size_t)slot] = (uint32_t)records; X.mut_used += records;
+  return base;
 }
 
 // What every call on the store starts with; `need_tree`: the resident tree is read (and so must not be out on its slabs).
@@ -111,17 +133,29 @@ emat_status emat_tree_sample_push(emat_backend* h, int32_t* index) {
     X.is_tip.resize((size_t)X.n);
     for (int32_t v = 0; v < X.n; ++v) X.is_tip[(size_t)v] = k[2 * v] == EMAT_NO_NODE;
   }
+  if (X.mut_capacity > 0) {   // lists, the used part of the heap and the reference sequence go with it (gt_require has finished any gather: used[0] and the device's sequence are current)
+    st = mcc_mut_room_for(h, w, (int64_t)h->gt.used[0]); if (st) return st;
+    if (!h->have_ref) return fail(h, EMAT_ERR_STATE, w + ": emat_set_ref_sequence first (a sample that keeps its mutations keeps the sequence its root starts from)");
+  }
   hipLaunchKernelGGL(k_mcc_push, dim3((unsigned)((X.n + 255) / 256)), dim3(256), 0, h->stream, h->gt.dev(), mcc_store_dev(X), X.count);
   HIP_TRY(hipGetLastError());
+  if (X.mut_capacity > 0) {
+    const size_t n = (size_t)X.n, L = (size_t)X.mut_L, used = (size_t)h->gt.used[0];
+    const int64_t base = mcc_mut_take(X, X.count, (int64_t)used);
+    HIP_TRY(hipMemcpyAsync(X.mut_hdr.p + (size_t)X.count * n, h->gt.muts.p, n * sizeof(GList), hipMemcpyDeviceToDevice, h->stream));
+    if (used) HIP_TRY(hipMemcpyAsync(X.mut_arena.p + base, h->gt.mut_heap.p, used * sizeof(MutRec), hipMemcpyDeviceToDevice, h->stream));
+    if (!h->model_dirty && h->d_ref.n >= L) HIP_TRY(hipMemcpyAsync(X.mut_ref.p + (size_t)X.count * L, h->d_ref.p, L, hipMemcpyDeviceToDevice, h->stream));
+    else { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipMemcpy(X.mut_ref.p + (size_t)X.count * L, h->ref.data(), L, hipMemcpyHostToDevice)); }   // (no launch has brought the model to the device yet: the host's copy is the current one)
+  }
   if (index) *index = X.count;
   ++X.count;
   return EMAT_OK;
 }
 
-/* (header: emat_tree_sample_push_flat) */
-emat_status emat_tree_sample_push_flat(emat_backend* h, int32_t num_nodes, const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* t, int32_t root, int32_t* index) {
-  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
-  const std::string w = "emat_tree_sample_push_flat";
+}  // extern "C"
+namespace {
+// emat_tree_sample_push_flat and emat_tree_sample_push_flat_mutations: the checks of the tree, all made before anything is written ...
+emat_status mcc_push_flat_check(emat_backend* h, const std::string& w, int32_t num_nodes, const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* t, int32_t root) {
   emat_status st = mcc_require(h, w, false); if (st) return st;
   st = mcc_require_store(h, w); if (st) return st;
   MccHost& X = h->mcc;
@@ -130,14 +164,135 @@ emat_status emat_tree_sample_push_flat(emat_backend* h, int32_t num_nodes, const
   if (X.count >= X.capacity) return fail(h, EMAT_ERR_CAPACITY, w + ": the store is full (" + std::to_string(X.capacity) + " samples): nothing is evicted; emat_tree_samples_clear, or reserve more");
   const std::string msg = mcc_validate_flat(X.n, parent, child0, child1, root, X.is_tip);
   if (!msg.empty()) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": " + msg);
+  return EMAT_OK;
+}
+// ... and the copies into the next slot (the count is the caller's to advance).
+emat_status mcc_push_flat_copy(emat_backend* h, const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* t, int32_t root) {
+  MccHost& X = h->mcc;
   if (X.is_tip.empty()) { X.is_tip.resize((size_t)X.n); for (int32_t v = 0; v < X.n; ++v) X.is_tip[(size_t)v] = child0[v] == EMAT_NO_NODE; }
   const size_t o = (size_t)X.count * (size_t)X.n, n = (size_t)X.n;
   HIP_TRY(hipStreamSynchronize(h->stream));   // (a derivation may still be reading the store)
   HIP_TRY(hipMemcpy(X.parent.p + o, parent, n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(X.c0.p + o, child0, n * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(X.c1.p + o, child1, n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(X.t.p + o, t, n * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(X.root.p + X.count, &root, 4, hipMemcpyHostToDevice));
+  return EMAT_OK;
+}
+}  // namespace
+extern "C" {
+
+/* (header: emat_tree_sample_push_flat) */
+emat_status emat_tree_sample_push_flat(emat_backend* h, int32_t num_nodes, const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* t, int32_t root, int32_t* index) {
+  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
+  const std::string w = "emat_tree_sample_push_flat";
+  emat_status st = mcc_push_flat_check(h, w, num_nodes, parent, child0, child1, t, root); if (st) return st;
+  st = mcc_push_flat_copy(h, parent, child0, child1, t, root); if (st) return st;
+  MccHost& X = h->mcc;
+  if (X.mut_capacity > 0) mcc_mut_take(X, X.count, -1);   // (a tree without its mutations: the site-state prober refuses this sample)
   if (index) *index = X.count;
   ++X.count;
+  return EMAT_OK;
+}
+
+/* a base tree read from a file with its mutations, as tools/delphy_mcc.cpp reads them (header: emat_tree_sample_push_flat_mutations) */
+emat_status emat_tree_sample_push_flat_mutations(emat_backend* h, int32_t num_nodes, const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* t, int32_t root,
+                                                 const int32_t* mut_offset, const int32_t* mut_site, const uint8_t* mut_from, const uint8_t* mut_to, const double* mut_t, const uint8_t* ref_sequence, int32_t* index) {
+  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
+  const std::string w = "emat_tree_sample_push_flat_mutations";
+  emat_status st = mcc_push_flat_check(h, w, num_nodes, parent, child0, child1, t, root); if (st) return st;
+  MccHost& X = h->mcc;
+  if (X.mut_capacity == 0) return fail(h, EMAT_ERR_STATE, w + ": emat_tree_samples_reserve_mutations first (this store keeps topology and times only)");
+  if (!mut_offset || !ref_sequence) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": mut_offset and ref_sequence must be given");
+  const int32_t n = X.n, L = h->L;
+  if (mut_offset[0] != 0) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": mut_offset must start at 0, not " + std::to_string(mut_offset[0]));
+  for (int32_t v = 0; v < n; ++v)
+    if (mut_offset[v + 1] < mut_offset[v]) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": mut_offset must not decrease: node " + std::to_string(v) + " has " + std::to_string(mut_offset[v]) + " and then " + std::to_string(mut_offset[v + 1]));
+  const int32_t nm = mut_offset[n];
+  if (nm > 0 && (!mut_site || !mut_from || !mut_to || !mut_t)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": mut_site, mut_from, mut_to and mut_t must be given");
+  for (int32_t k = 0; k < nm; ++k) {
+    if (mut_site[k] < 0 || mut_site[k] >= L) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": mutation " + std::to_string(k) + ": site " + std::to_string(mut_site[k]) + " is outside the valid range [0, " + std::to_string(L) + ")");
+    if (mut_from[k] > 3 || mut_to[k] > 3) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": mutation " + std::to_string(k) + ": states must be 0..3, not " + std::to_string(mut_from[k]) + " -> " + std::to_string(mut_to[k]));
+  }
+  for (int32_t l = 0; l < L; ++l) if (ref_sequence[l] > 3) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": reference sequence states must be 0..3, and site " + std::to_string(l) + " has " + std::to_string(ref_sequence[l]));
+  st = mcc_mut_room_for(h, w, nm); if (st) return st;
+  std::vector<GList> hdr((size_t)n); std::vector<MutRec> rec((size_t)nm);
+  for (int32_t v = 0; v < n; ++v) hdr[(size_t)v] = GList{(uint32_t)mut_offset[v], (uint32_t)(mut_offset[v + 1] - mut_offset[v])};
+  for (int32_t k = 0; k < nm; ++k) { MutRec r{}; r.t = mut_t[k]; r.site = mut_site[k]; r.from = mut_from[k]; r.to = mut_to[k]; rec[(size_t)k] = r; }
+  st = mcc_push_flat_copy(h, parent, child0, child1, t, root); if (st) return st;
+  HIP_TRY(hipMemcpy(X.mut_hdr.p + (size_t)X.count * (size_t)n, hdr.data(), (size_t)n * sizeof(GList), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(X.mut_ref.p + (size_t)X.count * (size_t)L, ref_sequence, (size_t)L, hipMemcpyHostToDevice));
+  if (nm) HIP_TRY(hipMemcpy(X.mut_arena.p + X.mut_used, rec.data(), (size_t)nm * sizeof(MutRec), hipMemcpyHostToDevice));
+  mcc_mut_take(X, X.count, nm);
+  if (index) *index = X.count;
+  ++X.count;
+  return EMAT_OK;
+}
+
+/* (header: emat_tree_samples_reserve_mutations) */
+emat_status emat_tree_samples_reserve_mutations(emat_backend* h, int64_t mutation_records) {
+  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
+  const std::string w = "emat_tree_samples_reserve_mutations";
+  emat_status st = gt_require(h, false, true); if (st) return st;
+  MccHost& X = h->mcc;
+  if (mutation_records < 0) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": mutation_records must not be negative, not " + std::to_string(mutation_records));
+  if (X.capacity == 0) return fail(h, EMAT_ERR_STATE, w + ": emat_tree_samples_reserve first");
+  if (X.count > 0) return fail(h, EMAT_ERR_STATE, w + ": the store holds " + std::to_string(X.count) + " samples: emat_tree_samples_clear first (nothing is dropped silently)");
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  X.release_mutations();   // (freed first, so that the room asked for is the room needed)
+  if (mutation_records == 0) return EMAT_OK;
+  const size_t slots = (size_t)X.capacity, n = (size_t)X.n, L = (size_t)h->L, records = (size_t)mutation_records;
+  if (mutation_records > ((int64_t)1 << 40)) return fail(h, EMAT_ERR_CAPACITY, w + ": " + std::to_string(mutation_records) + " mutation records are more than any device holds");
+  const size_t hdr_bytes = slots * n * sizeof(GList), ref_bytes = slots * L, arena_bytes = records * sizeof(MutRec);
+  st = mcc_check_room(h, w, hdr_bytes + ref_bytes + arena_bytes, "the mutations of " + std::to_string(slots) + " samples (" + mcc_mb(hdr_bytes) + " of list headers, " + mcc_mb(ref_bytes) + " of reference sequences of " + std::to_string(L) +
+                                                                 " sites, " + mcc_mb(arena_bytes) + " for " + std::to_string(mutation_records) + " records)");
+  if (st) return st;
+  HIP_TRY(X.mut_hdr.alloc(slots * n)); HIP_TRY(X.mut_ref.alloc(slots * L)); HIP_TRY(X.mut_arena.alloc(records));
+  X.mut_capacity = mutation_records; X.mut_used = 0; X.mut_L = h->L; X.mut_slots = X.capacity; X.mut_n = X.n;
+  X.mut_base.assign(slots, -1); X.mut_len.assign(slots, 0);
+  return EMAT_OK;
+}
+
+/* (header: emat_tree_samples_mutation_info) */
+emat_status emat_tree_samples_mutation_info(emat_backend* h, int64_t* records_used, int64_t* records_capacity, int32_t* num_sites) {
+  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
+  emat_status st = gt_require(h, false, true); if (st) return st;
+  if (records_used) *records_used = h->mcc.mut_used;
+  if (records_capacity) *records_capacity = h->mcc.mut_capacity;
+  if (num_sites) *num_sites = h->mcc.mut_L;
+  return EMAT_OK;
+}
+
+/* one slot's mutations back as CSR in node order, and its reference sequence (header: emat_tree_sample_get_mutations) */
+emat_status emat_tree_sample_get_mutations(emat_backend* h, int32_t index, int32_t* mut_offset, int32_t* site, uint8_t* from, uint8_t* to, double* t, int64_t capacity, uint8_t* ref_sequence, int64_t* num_mutations) {
+  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
+  const std::string w = "emat_tree_sample_get_mutations";
+  emat_status st = gt_require(h, false, true); if (st) return st;
+  MccHost& X = h->mcc;
+  if (X.mut_capacity == 0) return fail(h, EMAT_ERR_STATE, w + ": emat_tree_samples_reserve_mutations first (this store keeps topology and times only)");
+  if (index < 0 || index >= X.count) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": sample " + std::to_string(index) + " is outside the valid range [0, " + std::to_string(X.count) + ")");
+  if (X.mut_base[(size_t)index] < 0) return fail(h, EMAT_ERR_STATE, w + ": sample " + std::to_string(index) + " was pushed without mutations (emat_tree_sample_push_flat)");
+  const size_t n = (size_t)X.n, L = (size_t)X.mut_L, len = (size_t)X.mut_len[(size_t)index];
+  if (num_mutations) *num_mutations = (int64_t)len;
+  const bool records = site || from || to || t;
+  if (records && capacity < (int64_t)len) return fail(h, EMAT_ERR_CAPACITY, w + ": sample " + std::to_string(index) + " has " + std::to_string(len) + " mutations, room for " + std::to_string(capacity));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (ref_sequence) HIP_TRY(hipMemcpy(ref_sequence, X.mut_ref.p + (size_t)index * L, L, hipMemcpyDeviceToHost));
+  if (!mut_offset && !records) return EMAT_OK;
+  std::vector<GList> hdr(n); std::vector<MutRec> rec(len);
+  HIP_TRY(hipMemcpy(hdr.data(), X.mut_hdr.p + (size_t)index * n, n * sizeof(GList), hipMemcpyDeviceToHost));
+  if (len && records) HIP_TRY(hipMemcpy(rec.data(), X.mut_arena.p + X.mut_base[(size_t)index], len * sizeof(MutRec), hipMemcpyDeviceToHost));
+  size_t km = 0;
+  if (mut_offset) mut_offset[0] = 0;
+  for (size_t v = 0; v < n; ++v) {   // the segment holds the lists in the order the parts wrote them: back into node order
+    if ((size_t)hdr[v].off + hdr[v].cnt > len || km + hdr[v].cnt > len) return fail(h, EMAT_ERR_INTERNAL, w + ": a list of sample " + std::to_string(index) + " lies outside its segment");
+    for (uint32_t k = 0; k < hdr[v].cnt; ++k, ++km) {
+      const MutRec& r = rec[records ? hdr[v].off + k : 0];
+      if (site) site[km] = r.site;
+      if (from) from[km] = r.from;
+      if (to) to[km] = r.to;
+      if (t) t[km] = r.t;
+    }
+    if (mut_offset) mut_offset[v + 1] = (int32_t)km;
+  }
   return EMAT_OK;
 }
 
@@ -154,7 +309,7 @@ emat_status emat_tree_samples_clear(emat_backend* h) {
   if (!h) return EMAT_ERR_INVALID_ARGUMENT;
   emat_status st = gt_require(h, false, true); if (st) return st;
   MccHost& X = h->mcc;
-  X.count = 0; X.derived_M = 0; X.is_tip.clear();
+  X.count = 0; X.derived_M = 0; X.is_tip.clear(); X.mut_used = 0;   // (the arena is handed out afresh; its room stays)
   if (X.capacity > 0 && h->gt.resident && h->gt.n != X.n) return mcc_store_alloc(h, "emat_tree_samples_clear", X.capacity, h->gt.n);   // the store follows the resident tree's node count
   return EMAT_OK;
 }

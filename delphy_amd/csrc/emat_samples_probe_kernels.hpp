@@ -1,4 +1,5 @@
-// emat_samples_probe_kernels.hpp -- the ancestral prober over MANY sampled trees of the store at once, and the spread of its answers.
+// emat_samples_probe_kernels.hpp -- the ancestral prober over MANY sampled trees of the store at once, and the spread of its answers;
+// further down the site-state prober in the same shape, over (sample, site) pairs, for samples that kept their mutations.
 //
 // Reference: probe_ancestors_on_tree (core/ancestral_tree_prober.cpp:31-77) run on every base tree of an MCC tree, the marked nodes
 // of a base tree being the nodes that correspond to the MCC nodes picked (tools/delphy_wasm.cpp:1828-1849).  A sample of the store
@@ -44,7 +45,7 @@ struct SProbeChunk {                 // the samples [k0, k0 + B) of a call and t
   int32_t k0, B, n, num_members;
   int32_t stride_cells, pad;
 };
-enum SProbeStatus : int32_t { k_sprobe_ok = 0, k_sprobe_negative_branch = 1, k_sprobe_bad_link = 2 };
+enum SProbeStatus : int32_t { k_sprobe_ok = 0, k_sprobe_negative_branch = 1, k_sprobe_bad_link = 2, k_sprobe_bad_list = 4 };
 constexpr int k_sprobe_sort_max = 4096;       // samples the order statistics hold: 32 KB of LDS for a workgroup
 constexpr int k_sprobe_sort_threads = 256;
 
@@ -160,6 +161,90 @@ __global__ void __launch_bounds__(64) k_sprobe_chain(SProbeChunk C, int out_cell
     const double* pp = p_coalesce + (size_t)j * C.stride_cells;
     double* p_out = p_all + ((size_t)(C.k0 + j) * C.num_members + m) * out_cells;
     double p = m == C.num_members - 1 ? 1.0 : 0.0;
+    for (int c = 0; c < num_cells; ++c) {
+      const double tot = tt[c], pc = pp[c];
+      const double pc_cat = tot == 0.0 ? 0.0 : pc * (cnt[c] / tot);
+      p = pc_cat + (1.0 - pc) * p;
+      if (c >= cells_to_skip && c - cells_to_skip < out_cells) p_out[c - cells_to_skip] = p;
+    }
+  }
+}
+
+// ---- the site-state form ---------------------------------------------------------------------------------------------------
+// probe_site_states_on_tree (core/site_states_tree_prober.cpp:40-92) on samples that kept their mutations (emat_mcc_host.hpp:
+// emat_tree_samples_reserve_mutations).  The unit of work is a (sample, site) pair: the descriptor array holds one SProbeSample per
+// unit, sample-major (unit u = k * num_sites + i: sample k, entry i of `sites`), the 4 states are the members, and a unit owns the
+// working room a sample owns above.  So k_sprobe_jump_init, k_sprobe_jump_double, k_sprobe_counts and k_sprobe_cells run on units
+// as they are, and the results land as [count][num_sites][4][cells]; what differs is where the labels come from (the slot's lists),
+// the branches (trapezoids for a branch that carries a mutation of the site) and the chain's initial member (the root's state).
+// The status word stays one per SAMPLE: status [count].
+struct MccMuts {                     // what a slot keeps of its mutations
+  const GList* hdr;                  // [capacity * n] per-node lists: records [off, off + cnt) of the slot's segment
+  const uint8_t* ref;                // [capacity * L] the reference sequence the slot's root starts from
+  const MutRec* arena;               // the segments of all slots
+  int32_t L, pad;
+};
+struct SProbeSeg { long long base; uint32_t len, pad; };   // a chosen sample's segment: arena [base, base + len)
+
+// k_probe_site_flags on the lists of a slot.  A list that leaves its segment is not read: it sets the status word.
+__global__ void __launch_bounds__(256) k_sprobe_site_flags(MccStore S, MccMuts Mu, SProbeChunk C, const SProbeSeg* segs, const int32_t* sites, int num_sites, int32_t* val, int32_t* status) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= C.n) return;
+  for (int j = blockIdx.y; j < C.B; j += gridDim.y) {
+    const int u = C.k0 + j, k = u / num_sites;
+    const int32_t site = sites[u - k * num_sites], slot = C.samples[u].slot;
+    const SProbeSeg seg = segs[k];
+    GList l = Mu.hdr[(size_t)slot * C.n + v];
+    if ((unsigned long long)l.off + l.cnt > seg.len) { atomicOr(&status[k], (int32_t)k_sprobe_bad_list); l.cnt = 0; }
+    const MutRec* r = Mu.arena + seg.base + l.off;
+    int32_t s = -1;
+    if (v == S.root[slot]) {
+      s = Mu.ref[(size_t)slot * Mu.L + site];
+      for (uint32_t i = 0; i < l.cnt; ++i) if (r[i].site == site) s = r[i].to;
+    } else {
+      for (uint32_t i = 0; i < l.cnt; ++i) if (r[i].site == site) { s = r[i].to; break; }
+    }
+    val[(size_t)j * C.n + v] = s;
+  }
+}
+// k_probe_branches<true> on a slot of the store (4 members).
+__global__ void __launch_bounds__(256) k_sprobe_site_branches(MccStore S, SProbeChunk C, int num_sites, const int32_t* val, const int32_t* jump, unsigned long long* fix, int32_t* diff, int32_t* status) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= C.n) return;
+  for (int j = blockIdx.y; j < C.B; j += gridDim.y) {
+    const int u = C.k0 + j, k = u / num_sites;
+    const SProbeSample& s = C.samples[u];
+    const size_t in = (size_t)s.slot * C.n, o = (size_t)j * C.n;
+    if (v == S.root[s.slot]) continue;
+    const int32_t p = S.parent[in + v];
+    if ((uint32_t)p >= (uint32_t)C.n) { atomicOr(&status[k], (int32_t)k_sprobe_bad_link); continue; }
+    const int32_t top = val[o + jump[o + p]];
+    if ((uint32_t)top >= (uint32_t)C.num_members) continue;
+    const double left = S.t[in + p], right = S.t[in + v];
+    if (!(left <= right)) { atomicOr(&status[k], (int32_t)k_sprobe_negative_branch); continue; }
+    const ProbeGrid g = s.grid;
+    unsigned long long* f = fix + (size_t)j * C.num_members * C.stride_cells;
+    const int32_t own = val[o + v];
+    if (own >= 0 && own < C.num_members) {
+      probe_add_trapezoid(g, f, top, left, right, 1.0, 0.0);
+      probe_add_trapezoid(g, f, own, left, right, 0.0, 1.0);
+    } else probe_add_boxcar(g, f, diff + (size_t)j * C.num_members * (C.stride_cells + 1), top, left, right);
+  }
+}
+// k_probe_chain, starting in the state of the unit's root (val of the root, as k_sprobe_site_flags left it); p_all [units][4][out_cells].
+__global__ void __launch_bounds__(64) k_sprobe_site_chain(MccStore S, SProbeChunk C, int out_cells, const int32_t* val, const double* counts, const double* total, const double* p_coalesce, double* p_all) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= C.num_members) return;
+  for (int j = blockIdx.y; j < C.B; j += gridDim.y) {
+    const SProbeSample& s = C.samples[C.k0 + j];
+    const int num_cells = s.grid.num_cells, cells_to_skip = s.cells_to_skip;
+    const int32_t r = S.root[s.slot];
+    const int32_t initial = (uint32_t)r < (uint32_t)C.n ? val[(size_t)j * C.n + r] : -1;
+    const double* cnt = counts + (size_t)j * C.num_members * C.stride_cells + (size_t)m * num_cells;
+    const double* tt = total + (size_t)j * C.stride_cells;
+    const double* pp = p_coalesce + (size_t)j * C.stride_cells;
+    double* p_out = p_all + ((size_t)(C.k0 + j) * C.num_members + m) * out_cells;
+    double p = m == initial ? 1.0 : 0.0;
     for (int c = 0; c < num_cells; ++c) {
       const double tot = tt[c], pc = pp[c];
       const double pc_cat = tot == 0.0 ? 0.0 : pc * (cnt[c] / tot);

@@ -139,14 +139,15 @@ struct ProbeScratch {
   DevBuf<unsigned long long> sp_fix;
   DevBuf<double> sp_counts, sp_total, sp_p_coalesce, sp_p, sp_mean, sp_stats, sp_root_t, sp_sky_x, sp_sky_g;
   DevBuf<SProbeSample> sp_samples; DevBuf<PopTable> sp_pops;
+  DevBuf<SProbeSeg> sp_segs; DevBuf<int32_t> sp_sites;   // the site-state form: the chosen samples' segments of the mutation arena, the sites asked for
   template <class T> static void drop(DevBuf<T>& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 0; }
   size_t samples_bytes() const {
     return (sp_val.n + sp_jump_a.n + sp_jump_b.n + sp_marks.n + sp_diff.n + sp_status.n + sp_ranks.n) * 4 + (sp_fix.n + sp_counts.n + sp_total.n + sp_p_coalesce.n + sp_p.n + sp_mean.n + sp_stats.n + sp_root_t.n + sp_sky_x.n + sp_sky_g.n) * 8 +
-           sp_samples.n * sizeof(SProbeSample) + sp_pops.n * sizeof(PopTable);
+           sp_samples.n * sizeof(SProbeSample) + sp_pops.n * sizeof(PopTable) + sp_segs.n * sizeof(SProbeSeg) + sp_sites.n * 4;
   }
   void release_samples() {   // with the store (MccHost::release): what was sized by it goes with it
     drop(sp_val); drop(sp_jump_a); drop(sp_jump_b); drop(sp_marks); drop(sp_diff); drop(sp_status); drop(sp_ranks); drop(sp_fix); drop(sp_counts); drop(sp_total); drop(sp_p_coalesce);
-    drop(sp_p); drop(sp_mean); drop(sp_stats); drop(sp_root_t); drop(sp_sky_x); drop(sp_sky_g); drop(sp_samples); drop(sp_pops);
+    drop(sp_p); drop(sp_mean); drop(sp_stats); drop(sp_root_t); drop(sp_sky_x); drop(sp_sky_g); drop(sp_samples); drop(sp_pops); drop(sp_segs); drop(sp_sites);
   }
 };
 
@@ -161,8 +162,16 @@ struct MccHost {
   MccTable table{}; int32_t table_regrows = 0; int table_log2_hint = 0;   // the table of clade counts of the last derivation; the size it ended with is where the next one starts
   int32_t derived_M = 0, derived_n = 0;                // the (M x n) correspondence table of the last derivation is valid
   int32_t derived_first = 0, derived_stride = 1;       // ... and belongs to the samples derived_first + k * derived_stride (emat_mcc_probe_ancestors probes those)
+  // Opt-in (emat_tree_samples_reserve_mutations): what a slot keeps of its mutations, for the site-state prober over samples.  Per slot
+  // the per-node list headers and the reference sequence; the records of all slots in one arena, a slot's in one segment handed out
+  // here on the host (mut_base / mut_len; base -1: the sample came without mutations).  The headers' offsets are relative to the segment.
+  int64_t mut_capacity = 0, mut_used = 0;              // records of the arena, and how many are handed out; capacity 0: no room
+  int32_t mut_L = 0, mut_slots = 0, mut_n = 0;         // sites, slots and nodes the room was made for
+  DevBuf<GList> mut_hdr; DevBuf<uint8_t> mut_ref; DevBuf<MutRec> mut_arena;
+  std::vector<int64_t> mut_base; std::vector<uint32_t> mut_len;
   template <class T> static void drop(DevBuf<T>& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 0; }
-  void release() { drop(parent); drop(c0); drop(c1); drop(root); drop(t); drop(fp); drop(keys); drop(ntips); drop(arrive); drop(corr); drop(counts); drop(hist); drop(exact); capacity = 0; count = 0; derived_M = 0; table_log2_hint = 0; }
+  void release_mutations() { drop(mut_hdr); drop(mut_ref); drop(mut_arena); mut_capacity = 0; mut_used = 0; mut_L = 0; mut_slots = 0; mut_n = 0; mut_base.clear(); mut_len.clear(); }
+  void release() { drop(parent); drop(c0); drop(c1); drop(root); drop(t); drop(fp); drop(keys); drop(ntips); drop(arrive); drop(corr); drop(counts); drop(hist); drop(exact); release_mutations(); capacity = 0; count = 0; derived_M = 0; table_log2_hint = 0; }
 };
 
 }  // namespace emat
@@ -259,7 +268,7 @@ struct emat_backend {
   GTreeHost gt;                     // the whole tree, when it lives in HBM (emat_tree_upload)
   ProbeScratch probe;               // what emat_tree_probe_* / emat_tree_branch_counts work in
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
-  int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples emat_tree_samples_probe_ancestors works on at a time (0: as many as half the free memory holds)
+  int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs
   BuiltTree built;                  // what emat_tree_build_usher_like made, until it is fetched (emat_tree_built_get)
   bool cfg_taper = true;            // option "ticket_taper": tickets of a part shrink (10 : 6 : 3 : 1 for four tickets, else n : ... : 1) instead of being equal

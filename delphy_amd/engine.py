@@ -91,7 +91,8 @@ class _SamplesProbeResultC(C.Structure):
 
 @dataclass
 class SamplesProbe:
-    """What emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors return (include/emat_backend.h: emat_samples_probe_result)."""
+    """What emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors return (include/emat_backend.h: emat_samples_probe_result).
+    The site-state forms return the same with a site axis: `members` below reads [sites][4]."""
     p: Optional[np.ndarray]            # [count][members][cells] every chosen sample's probabilities, or None when not asked for
     mean: Optional[np.ndarray]         # [members][cells] their mean, added in sample order
     order_stats: Optional[np.ndarray]  # [ranks][members][cells] the ranks[j]-th smallest over the samples, or None without ranks
@@ -360,6 +361,12 @@ def load_library():
         "emat_mcc_derive": [B, i32, i32, i32, u64, P(_MccResultC)], "emat_mcc_get_correspondence": [B, i32, P(i32), P(C.c_uint8)],
         "emat_tree_samples_probe_ancestors": [B, P(_PopModelC), i32, i32, i32, i32, i32, P(i32), i32, dbl, dbl, i32, P(_SamplesProbeResultC)],
         "emat_mcc_probe_ancestors": [B, P(_PopModelC), i32, i32, P(i32), dbl, dbl, i32, P(_SamplesProbeResultC)], "emat_mcc_get_derivation": [B, P(i32), P(i32), P(i32)],
+        "emat_tree_samples_reserve_mutations": [B, i64],
+        "emat_tree_sample_push_flat_mutations": [B, i32, P(i32), P(i32), P(i32), P(dbl), i32, P(i32), P(i32), P(C.c_uint8), P(C.c_uint8), P(dbl), P(C.c_uint8), P(i32)],
+        "emat_tree_sample_get_mutations": [B, i32, P(i32), P(i32), P(C.c_uint8), P(C.c_uint8), P(dbl), i64, P(C.c_uint8), P(i64)],
+        "emat_tree_samples_mutation_info": [B, P(i64), P(i64), P(i32)],
+        "emat_tree_samples_probe_site_states": [B, P(_PopModelC), i32, i32, i32, i32, i32, P(i32), dbl, dbl, i32, P(_SamplesProbeResultC)],
+        "emat_mcc_probe_site_states": [B, P(_PopModelC), i32, i32, P(i32), dbl, dbl, i32, P(_SamplesProbeResultC)],
         "emat_run_note_device_reassembled": [R, i32, P(i32), P(C.c_uint8)], "emat_run_set_paranoid": [R, i32], "emat_run_set_reference_remainder": [R, i32],
     }
     M = C.c_void_p
@@ -784,14 +791,16 @@ class EmatBackend:
         self._ck(self._lib.emat_mcc_get_correspondence(self._h, k, _ptr(node, C.c_int32), _ptr(ex, C.c_uint8)), "emat_mcc_get_correspondence")
         return node, ex.astype(bool)
 
-    def _samples_probe(self, call, what, pops, count, num_marked, num_t_cells, ranks, per_sample, mean):
-        """The outputs of a batched probe and the call itself: `call(pop_array, num_pops, result)` makes it."""
+    def _samples_probe(self, call, what, pops, count, num_marked, num_t_cells, ranks, per_sample, mean, num_sites=None):
+        """The outputs of a batched probe and the call itself: `call(pop_array, num_pops, result)` makes it.  With `num_sites`
+        (the site-state forms) the member axis is two: [num_sites][4]."""
         pops = [pops] if isinstance(pops, PopModel) else list(pops)
         pop_c = (_PopModelC * max(len(pops), 1))(*[m.c_struct() for m in pops])
-        m, members, cells = max(count, 1), max(num_marked, 0) + 1, max(num_t_cells, 1)
+        m, cells = max(count, 1), max(num_t_cells, 1)
+        members = (max(num_marked, 0) + 1,) if num_sites is None else (max(num_sites, 1), 4)
         rk = np.ascontiguousarray([] if ranks is None else ranks, np.int32)
-        r = SamplesProbe(np.zeros((m, members, cells)) if per_sample else None, np.zeros((members, cells)) if mean else None,
-                         np.zeros((rk.shape[0], members, cells)) if rk.shape[0] else None, np.zeros(m, np.int32))
+        r = SamplesProbe(np.zeros((m,) + members + (cells,)) if per_sample else None, np.zeros(members + (cells,)) if mean else None,
+                         np.zeros((rk.shape[0],) + members + (cells,)) if rk.shape[0] else None, np.zeros(m, np.int32))
         c = _SamplesProbeResultC(_ptr(r.p, C.c_double) if per_sample else None, _ptr(r.mean, C.c_double) if mean else None, int(rk.shape[0]),
                                  _ptr(rk, C.c_int32) if rk.shape[0] else None, _ptr(r.order_stats, C.c_double) if rk.shape[0] else None, _ptr(r.cells_to_skip, C.c_int32))
         self._ck(call(pop_c, len(pops), C.byref(c)), what)
@@ -821,6 +830,68 @@ class EmatBackend:
         self._ck(self._lib.emat_mcc_get_derivation(self._h, None, C.byref(count), None), "emat_mcc_get_derivation")
         return self._samples_probe(lambda pc, npc, res: self._lib.emat_mcc_probe_ancestors(self._h, pc, npc, int(mk.shape[0]), _ptr(mk, C.c_int32) if mk.size else None, t_start, t_end, num_t_cells, res),
                                    "emat_mcc_probe_ancestors", pops, int(count.value), int(mk.shape[0]), num_t_cells, ranks, per_sample, mean)
+
+    # ---- samples that keep their mutations, and the site-state prober over them (include/emat_backend.h) ----
+    def tree_samples_reserve_mutations(self, mutation_records: int) -> None:
+        """On an empty store: room for every slot's list headers and reference sequence and an arena of `mutation_records` records
+        shared by all slots (0 releases it).  From then on tree_sample_push keeps the resident tree's mutations too."""
+        self._ck(self._lib.emat_tree_samples_reserve_mutations(self._h, int(mutation_records)), "emat_tree_samples_reserve_mutations")
+
+    def tree_sample_push_flat_mutations(self, parent, child0, child1, t, root: int, mut_offset, mut_site, mut_from, mut_to, mut_t, ref_sequence) -> int:
+        """tree_sample_push_flat for a tree that comes with its mutations (CSR lists per node) and its reference sequence."""
+        pa = np.ascontiguousarray(parent, np.int32); a0 = np.ascontiguousarray(child0, np.int32); a1 = np.ascontiguousarray(child1, np.int32); tt = np.ascontiguousarray(t, np.float64)
+        if not (pa.shape == a0.shape == a1.shape == tt.shape and pa.ndim == 1):
+            raise ValueError("parent, child0, child1 and t must be one-dimensional and of one length")
+        mo = np.ascontiguousarray(mut_offset, np.int32); ms = np.ascontiguousarray(mut_site, np.int32); mf = np.ascontiguousarray(mut_from, np.uint8)
+        mt = np.ascontiguousarray(mut_to, np.uint8); mtt = np.ascontiguousarray(mut_t, np.float64); ref = np.ascontiguousarray(ref_sequence, np.uint8)
+        if mo.shape != (pa.shape[0] + 1,) or not (ms.shape == mf.shape == mt.shape == mtt.shape and ms.ndim == 1) or ms.shape[0] < max(int(mo.max()), 0) or ref.shape != (self.num_sites,):
+            raise ValueError("mut_offset must have num_nodes + 1 entries, the four mutation arrays its last entry, and ref_sequence num_sites")
+        i = C.c_int32(-1)
+        opt = lambda a, ct: _ptr(a, ct) if a.shape[0] else None
+        self._ck(self._lib.emat_tree_sample_push_flat_mutations(self._h, int(pa.shape[0]), _ptr(pa, C.c_int32), _ptr(a0, C.c_int32), _ptr(a1, C.c_int32), _ptr(tt, C.c_double), int(root),
+                                                                _ptr(mo, C.c_int32), opt(ms, C.c_int32), opt(mf, C.c_uint8), opt(mt, C.c_uint8), opt(mtt, C.c_double), _ptr(ref, C.c_uint8), C.byref(i)),
+                 "emat_tree_sample_push_flat_mutations")
+        return int(i.value)
+
+    def tree_samples_mutation_info(self):
+        """(records handed out, records of the arena -- 0 without mutation room --, the number of sites the room is bound to)."""
+        used, cap, L = C.c_int64(), C.c_int64(), C.c_int32()
+        self._ck(self._lib.emat_tree_samples_mutation_info(self._h, C.byref(used), C.byref(cap), C.byref(L)), "emat_tree_samples_mutation_info")
+        return int(used.value), int(cap.value), int(L.value)
+
+    def tree_sample_get_mutations(self, index: int):
+        """(mut_offset [n + 1], site, from, to, t, ref_sequence) of one slot: CSR in node order, every list in its stored order."""
+        n = self.tree_samples_info()[2]
+        L = self.tree_samples_mutation_info()[2]
+        nm = C.c_int64(0)
+        self._ck(self._lib.emat_tree_sample_get_mutations(self._h, index, None, None, None, None, None, 0, None, C.byref(nm)), "emat_tree_sample_get_mutations")
+        k = int(nm.value)
+        off = np.zeros(n + 1, np.int32); site = np.zeros(k, np.int32); frm = np.zeros(k, np.uint8); to = np.zeros(k, np.uint8); t = np.zeros(k); ref = np.zeros(max(L, 1), np.uint8)
+        opt = lambda a, ct: _ptr(a, ct) if k else None
+        self._ck(self._lib.emat_tree_sample_get_mutations(self._h, index, _ptr(off, C.c_int32), opt(site, C.c_int32), opt(frm, C.c_uint8), opt(to, C.c_uint8), opt(t, C.c_double), k,
+                                                          _ptr(ref, C.c_uint8), C.byref(nm)), "emat_tree_sample_get_mutations")
+        return off, site, frm, to, t, ref[:L]
+
+    def tree_samples_probe_site_states(self, pops, sites, t_start: float, t_end: float, num_t_cells: int, first: int = 0, count: Optional[int] = None, stride: int = 1,
+                                       ranks=None, per_sample: bool = True, mean: bool = True) -> "SamplesProbe":
+        """probe_site_states_on_tree on the samples first, first + stride, ... of the store, for every site of `sites`, in one call.  p[k][i] is
+        what tree_probe_site_states gives for sample k's tree and reference sequence and sites[i], bit for bit: p [count][sites][4][cells],
+        mean [sites][4][cells], order_stats [ranks][sites][4][cells]."""
+        held = self.tree_samples_info()[0]
+        if count is None:
+            count = max(0, (held - first + stride - 1) // stride) if stride >= 1 and first >= 0 else 0
+        st = np.ascontiguousarray(sites, np.int32).reshape(-1)
+        return self._samples_probe(lambda pc, npc, res: self._lib.emat_tree_samples_probe_site_states(self._h, pc, npc, first, count, stride, int(st.shape[0]), _ptr(st, C.c_int32) if st.size else None,
+                                                                                                       t_start, t_end, num_t_cells, res),
+                                   "emat_tree_samples_probe_site_states", pops, count, 0, num_t_cells, ranks, per_sample, mean, num_sites=int(st.shape[0]))
+
+    def mcc_probe_site_states(self, pops, sites, t_start: float, t_end: float, num_t_cells: int, ranks=None, per_sample: bool = True, mean: bool = True) -> "SamplesProbe":
+        """The same on every base tree of the last mcc_derive."""
+        st = np.ascontiguousarray(sites, np.int32).reshape(-1)
+        count = C.c_int32(0)
+        self._ck(self._lib.emat_mcc_get_derivation(self._h, None, C.byref(count), None), "emat_mcc_get_derivation")
+        return self._samples_probe(lambda pc, npc, res: self._lib.emat_mcc_probe_site_states(self._h, pc, npc, int(st.shape[0]), _ptr(st, C.c_int32) if st.size else None, t_start, t_end, num_t_cells, res),
+                                   "emat_mcc_probe_site_states", pops, int(count.value), 0, num_t_cells, ranks, per_sample, mean, num_sites=int(st.shape[0]))
 
     def tree_counters(self):
         """(growths of the cut-state pools, growths of the list heaps, cut-point states that needed the large kernel) of the

@@ -120,7 +120,7 @@ emat_status emat_backend_destroy(emat_backend* h);
  *   site partition and nu_l == 1 everywhere, where the answers are known without a load: the A/B of that short cut, round 6),
  *   "debug_fail_gather" (1: the next deferred gather of the device-resident tree reports an inconsistency; may be set at any time);
  *   "mcc_table_log2" (log2 of the slots emat_mcc_derive's table of clade counts starts with, 0 = four per node: a small value makes it grow; may be set at any time);
- *   "samples_probe_chunk" (samples emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors work on at a time, 0 = as many as fit: results do not depend on it; may be set at any time);
+ *   "samples_probe_chunk" (samples emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors and the site-state forms work on at a time, 0 = as many as fit: results do not depend on it; may be set at any time);
  *   profiling builds: "fn_min_lists", "phase_extra". */
 emat_status emat_set_option(emat_backend* h, const char* key, const char* value);
 /* Size of the library's host thread pool (per process, before its first parallel loop; 0 = default: min(cores, 16)). */
@@ -372,8 +372,8 @@ emat_status emat_mcc_get_correspondence(emat_backend* h, int32_t k, int32_t* nod
  *                   4 096 samples when order statistics are asked for (the sort's workgroup holds them in LDS): more is
  *                   EMAT_ERR_CAPACITY.
  * Only what is asked for crosses to the host.  Both calls touch only the store: like emat_mcc_derive they may be called while the
- * parts are out, and their launches queue on the engine's stream; with several processes rank 0 answers alone.  There is no
- * site-state form: samples do not hold mutations.  The samples are worked on in chunks sized from the free device memory (per
+ * parts are out, and their launches queue on the engine's stream; with several processes rank 0 answers alone.  The site-state
+ * form is the next section: it needs samples that kept their mutations.  The samples are worked on in chunks sized from the free device memory (per
  * sample about 12 bytes a node and 28 bytes per member and cell); the results are the same bits for every chunk size, and option
  * "samples_probe_chunk" (0 = automatic; may be set at any time) forces one for tests.
  *
@@ -395,7 +395,7 @@ emat_status emat_mcc_get_correspondence(emat_backend* h, int32_t k, int32_t* nod
  * (emat_tree_sample_push_flat does not check times); the text names the sample's position.  EMAT_ERR_NO_DEVICE: a handle without a
  * device.  After any refusal the next call works. */
 typedef struct emat_samples_probe_result {
-  double*  p;             /* [count][num_marked + 1][num_t_cells], or NULL: every chosen sample's probabilities */
+  double*  p;             /* [count][num_marked + 1][num_t_cells], or NULL: every chosen sample's probabilities (site-state form: [count][num_sites][4][num_t_cells], and so on below) */
   double*  mean;          /* [num_marked + 1][num_t_cells], or NULL: ((p_0 + p_1) + ... + p_{count-1}) / count, summed in sample order */
   int32_t  num_ranks;     /* 0, or how many order statistics */
   const int32_t* ranks;   /* [num_ranks], each in [0, count) */
@@ -411,6 +411,74 @@ emat_status emat_mcc_probe_ancestors(emat_backend* h, const emat_pop_model* pop_
     int32_t num_marked, const int32_t* mcc_nodes,
     double t_start, double t_end, int32_t num_t_cells, emat_samples_probe_result* out);
 emat_status emat_mcc_get_derivation(emat_backend* h, int32_t* first, int32_t* count, int32_t* stride);
+/* ---- samples that keep their mutations, and the site-state prober over all kept samples in one call --------------------------
+ * The second curve a front end draws over every base tree of an MCC tree: probe_site_states_on_tree
+ * (core/site_states_tree_prober.cpp:40-92, exported at tools/delphy_wasm.cpp:1809), the prevalence of a site's four states over time,
+ * with the same band over the samples.  That prober reads a tree's mutations and the sequence its root starts from, which a sample of
+ * the store does not have unless the store is told to keep them.  Opt-in: a store without this room behaves exactly as before.
+ *
+ *   emat_tree_samples_reserve_mutations  after emat_tree_samples_reserve, on an empty store (one that holds samples is
+ *                               EMAT_ERR_STATE: clear it first): room for the per-node list headers of `capacity` samples
+ *                               (capacity x n x 8 bytes), the reference sequence of every slot (capacity x L bytes, L = the handle's
+ *                               num_sites) and an arena of `mutation_records` records of 16 bytes shared by all slots (a Mutation,
+ *                               core/mutations.h:21-29).  hipMemGetInfo is asked first: more than is free is EMAT_ERR_CAPACITY with the
+ *                               three sizes in emat_last_error.  0 releases the room.  A later emat_tree_samples_reserve (or the
+ *                               re-binding emat_tree_samples_clear does after the node count changed) that re-allocates the store, or
+ *                               changes its slots or node count, DROPS this room: reserve it again.
+ *   emat_tree_sample_push       on a store with that room also keeps the resident tree's list headers, the used part of its mutation
+ *                               heap (as one segment of the arena; the headers' offsets stay as they are, relative to the segment)
+ *                               and the reference sequence as it stands on the device (Base_tree_vector::push_back copies the whole
+ *                               Phylo_tree, delphy_ui.cpp:770-773): device to device on the engine's stream.  An arena without room
+ *                               for this tree's records is EMAT_ERR_CAPACITY (records needed and free in the text): nothing is
+ *                               pushed and the count is unchanged.
+ *   emat_tree_sample_push_flat_mutations  emat_tree_sample_push_flat for a tree that comes with its mutations as CSR lists
+ *                               (mut_offset [n + 1]; a file's trees, tools/delphy_mcc.cpp) and its reference sequence [L].  On top of
+ *                               emat_tree_sample_push_flat's checks: offsets start at 0 and never decrease, sites are in [0, L), states
+ *                               in [0, 4) here and in ref_sequence.  That the states chain along the tree is NOT checked.  The root may
+ *                               carry mutations.  emat_tree_sample_push_flat itself still works on such a store: its sample is marked
+ *                               as having no mutations, and the site-state calls refuse a range that includes it.
+ *   emat_tree_sample_get_mutations  one slot's mutations back as CSR in node order, each list in its stored order, and its reference
+ *                               sequence (Phylo_tree::ref_sequence); any array may be NULL.  `capacity` (records) too small is
+ *                               EMAT_ERR_CAPACITY with *num_mutations set.
+ *   emat_tree_samples_mutation_info  records handed out, records of the arena (0: no room), and the L the room is bound to.
+ *   emat_tree_samples_clear     hands the arena out afresh and keeps the room.
+ * The store binds to ONE number of sites, as to one node count.
+ *
+ *   emat_tree_samples_probe_site_states  for sample k (slot first + k * stride) and entry i of `sites`:
+ *     p[k][i]       [4][num_t_cells], BIT FOR BIT what emat_tree_probe_site_states returns for that sample's tree, reference sequence,
+ *                   population model and sites[i]: a branch takes the first mutation of the site on its list; the root starts from the
+ *                   slot's reference state with every mutation of the site on its own list applied, and that state is the chain's
+ *                   initial member; grid extension per sample against its own root (site_states_tree_prober.cpp:60-69), the
+ *                   fixed-point quantum of the store's node count, the same add_boxcar / add_trapezoid, intensity and exp.
+ *     mean, order_stats   as for the ancestral form, over the samples, for every (site entry, state, cell)
+ *     Dimensions of emat_samples_probe_result here, "members" being 4 x num_sites:  p [count][num_sites][4][num_t_cells];
+ *     mean [num_sites][4][num_t_cells];  order_stats [num_ranks][num_sites][4][num_t_cells];  cells_to_skip [count].
+ *     A site may be given twice.  The number of launches grows neither with count nor with num_sites: the chunks iterate over
+ *     (sample, site) pairs, "samples_probe_chunk" counting samples, each with all its sites; results are the same bits for every
+ *     chunk size.  Touches only the store: may be called while the parts are out; rank 0 answers alone.
+ *   emat_mcc_probe_site_states           the same with the first / count / stride of the last emat_mcc_derive
+ *     (emat_mcc_get_derivation sizes the outputs).  Sites are the same in every base tree: the correspondence table plays no part.
+ * EMAT_ERR_INVALID_ARGUMENT: what the ancestral batched call refuses of samples, models, window, ranks and outputs, with its texts;
+ * num_sites < 1 or sites NULL; a site outside [0, L) (the text names the entry).  EMAT_ERR_STATE: a store without mutation room; a
+ * chosen sample pushed without mutations (the text names its position and slot); emat_mcc_probe_site_states without a valid
+ * derivation.  EMAT_ERR_CAPACITY: the grid of a (sample, site) beyond emat_tree_probe_site_states' limits; results, or the working room
+ * of one sample with all its sites, beyond the free device memory (sizes in the text); order statistics over more than 4 096 samples.
+ * EMAT_ERR_INTERNAL: a bad link, a node earlier than its parent, or a list outside its segment in a sample (position in the text).
+ * EMAT_ERR_NO_DEVICE: a handle without a device.  After any refusal the next call works. */
+emat_status emat_tree_samples_reserve_mutations(emat_backend* h, int64_t mutation_records);
+emat_status emat_tree_sample_push_flat_mutations(emat_backend* h, int32_t num_nodes, const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* t, int32_t root,
+    const int32_t* mut_offset /* [num_nodes + 1] */, const int32_t* mut_site, const uint8_t* mut_from, const uint8_t* mut_to, const double* mut_t,
+    const uint8_t* ref_sequence /* [num_sites] */, int32_t* index);
+emat_status emat_tree_sample_get_mutations(emat_backend* h, int32_t index, int32_t* mut_offset /* [n + 1] */, int32_t* site, uint8_t* from, uint8_t* to, double* t,
+    int64_t capacity, uint8_t* ref_sequence /* [num_sites] */, int64_t* num_mutations);
+emat_status emat_tree_samples_mutation_info(emat_backend* h, int64_t* records_used, int64_t* records_capacity, int32_t* num_sites);
+emat_status emat_tree_samples_probe_site_states(emat_backend* h,
+    const emat_pop_model* pop_models, int32_t num_pop_models /* 1: one for all; count: one per chosen sample */,
+    int32_t first, int32_t count, int32_t stride, int32_t num_sites, const int32_t* sites /* [num_sites] */,
+    double t_start, double t_end, int32_t num_t_cells, emat_samples_probe_result* out);
+emat_status emat_mcc_probe_site_states(emat_backend* h, const emat_pop_model* pop_models, int32_t num_pop_models,
+    int32_t num_sites, const int32_t* sites /* [num_sites] */,
+    double t_start, double t_end, int32_t num_t_cells, emat_samples_probe_result* out);
 /* One run over several processes, one GPU each, EVERY one with the whole tree in its HBM (the tree is a few tens of MB; what
  * is worth sharding is the moves).  Every process cuts the same partition and calls emat_tree_repartition_range with its own
  * block [part_lo, part_hi) of the parts (backend part id = part - part_lo): the sequence states at the cut points and the

@@ -8,7 +8,10 @@ Medians of >= 20 calls in one process, synchronise included:
   * with --samples-probe: emat_mcc_probe_ancestors over the samples of each derivation (16 MCC nodes picked at random among the inner nodes
     with support < 1, 200 cells) in four modes -- the mean alone; the mean and three order statistics (2.5 %, 50 %, 97.5 %); everything copied
     back; the mean alone with the chunk forced to one sample -- and, beside them, the unchanged emat_tree_probe_ancestors on the resident tree
-    with 16 marks, which a loop over the samples would call M times.
+    with 16 marks, which a loop over the samples would call M times.  The store then also keeps every sample's mutations (the pushes of the
+    cycles are pushes WITH mutation room; a push without it is measured at the end, on the store cleared and its room released), and
+    emat_mcc_probe_site_states is timed for 1 and 8 sites (the sites the resident tree mutates most; 200 cells, the mean and three order
+    statistics) beside the unchanged emat_tree_probe_site_states on the resident tree, which a loop would call M x sites times.
 
     python scripts/mcc_probe.py [--samples 32,256,1000] [--moves-per-part 50] [--host-model] [--samples-probe] > profiles/mcc_probe_latest.json
 """
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--host-model", action="store_true")
     ap.add_argument("--samples-probe", action="store_true")
     a = ap.parse_args()
+    if a.host_model and a.samples_probe: ap.error("--host-model reads the samples --samples-probe has cleared by then: run them apart")
     sizes = sorted(int(x) for x in a.samples.split(","))
     sc = make_scenario(a.config)
     b = d.EmatBackend(sc.num_sites)
@@ -54,7 +58,9 @@ def main():
     try:
         for cycle in range(sizes[-1]):
             run.repartition()
-            if cycle == 0: b.tree_samples_reserve(sizes[-1] + a.calls)
+            if cycle == 0:
+                b.tree_samples_reserve(sizes[-1] + a.calls)
+                if a.samples_probe: b.tree_samples_reserve_mutations((sizes[-1] + a.calls) * (2 * int(sc.tree.mut_offset[sc.tree.num_nodes]) + 4096))
             run.run_moves(a.parts * a.moves_per_part); b.synchronize()
             run.reassemble(); b.synchronize()
             t0 = time.perf_counter(); b.tree_sample_push(); b.synchronize(); t1 = time.perf_counter()
@@ -98,6 +104,27 @@ def main():
                 row["M_single_tree_calls_ms"] = M * out["samples_probe"]["single_tree_probe_ancestors_ms"]
                 out["samples_probe"]["by_M"].append(row)
                 print("samples probe", row, file=sys.stderr, flush=True)
+            # the site-state form: samples that kept their mutations
+            per_site = np.bincount(sc.tree.mut_site[:int(sc.tree.mut_offset[sc.tree.num_nodes])], minlength=sc.num_sites)
+            busy = [int(v) for v in np.argsort(-per_site, kind="stable")[:8]]
+            used, cap, _ = b.tree_samples_mutation_info()
+            st = {"cells": 200, "sites": busy, "mutation_records_per_sample": used / b.tree_samples_count(), "arena_records": cap,
+                  "push_with_mutation_room_after_reassemble_ms": out["push_after_reassemble_ms"], "push_with_mutation_room_repeated_ms": out["push_repeated_ms"],
+                  "single_tree_probe_site_states_ms": median_ms(lambda: b.tree_probe_site_states(sc.pop, busy[0], *window), a.calls), "by_M": []}
+            for M in sizes:
+                b.mcc_derive(0, M, 1, seed=1)
+                ranks = [int(round(q * (M - 1))) for q in (0.025, 0.5, 0.975)]
+                calls = a.calls if M <= 256 else 5
+                row = {"M": M, "ranks": ranks}
+                for num_sites in (1, 8):
+                    b.mcc_probe_site_states(sc.pop, busy[:num_sites], *window, per_sample=False, ranks=ranks)      # (first call: allocations)
+                    row["mean_and_three_ranks_%d_sites_ms" % num_sites] = median_ms(lambda: b.mcc_probe_site_states(sc.pop, busy[:num_sites], *window, per_sample=False, ranks=ranks), calls)
+                    row["M_x_%d_single_tree_calls_ms" % num_sites] = M * num_sites * st["single_tree_probe_site_states_ms"]
+                st["by_M"].append(row)
+                print("samples site states", row, file=sys.stderr, flush=True)
+            b.tree_samples_clear(); b.tree_samples_reserve_mutations(0)
+            st["push_without_mutation_room_repeated_ms"] = median_ms(lambda: (b.tree_sample_push(), b.synchronize()), a.calls)
+            out["samples_site_states"] = st
         if a.host_model:
             import mcc_model as mm
             ss = [mm.Sample(*b.tree_sample_get(i)) for i in range(min(32, sizes[-1]))]
