@@ -27,6 +27,7 @@
 #include "emat_slab.hpp"
 #include "emat_reform_pure.hpp"
 #include "emat_rng_pos.hpp"
+#include "emat_gamma_pure.hpp"
 
 #ifndef EMAT_DEVICE_COMMON_ONCE_
 #define EMAT_DEVICE_COMMON_ONCE_
@@ -299,9 +300,7 @@ EMAT_D void rng_leave_leg(const Ctx& c, SlabHeader& h) {
   h.rng_counter = rng_pos_counter(c.rng_base, pos); h.rng_has_spare = rng_pos_has_spare(pos);
   h.rng_spare = rng_pos_in_buffer(sw, k_rng_blocks) ? rng_buffer_word(sw) : c.rng_spare;
 }
-EMAT_D double to_co(uint64_t a) { return (double)(a >> 11) * 0x1.0p-53; }
-EMAT_D double to_oo(uint64_t a) { return ((double)(a >> 12) + 0.5) * 0x1.0p-52; }
-EMAT_D double to_oc(uint64_t a) { return ((double)(a >> 11) + 1.0) * 0x1.0p-53; }
+using ::emat::to_co; using ::emat::to_oo; using ::emat::to_oc;   // 64 bits -> [0, 1), (0, 1), (0, 1]: emat_gamma_pure.hpp, shared with the site-rate moves
 EMAT_D double u01_co(Ctx& c) { return to_co(rng_next64(c)); }
 EMAT_D double u01_oo(Ctx& c) { return to_oo(rng_next64(c)); }
 EMAT_D double u01_oc(Ctx& c) { return to_oc(rng_next64(c)); }

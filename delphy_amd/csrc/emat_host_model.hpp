@@ -15,6 +15,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "emat_gamma_pure.hpp"
 #include "flat_tree.hpp"
 #include "host_parallel.hpp"
 
@@ -22,15 +23,7 @@ namespace emat {
 
 struct HostRng {
   uint64_t key = 0, counter = 0;
-  static void philox(uint64_t ctr, uint64_t key, uint32_t out[4]) {
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0, c3 = 0, k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-    for (int r = 0; r < 10; ++r) {
-      uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-      uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-      c0 = n0; c1 = n1; c2 = n2; c3 = n3; k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-  }
+  static void philox(uint64_t ctr, uint64_t key, uint32_t out[4]) { philox4x32_10_pure(ctr, key, out); }   // (emat_gamma_pure.hpp: the plain C++ spelling)
   uint64_t spare = 0; bool has_spare = false;   // second 64-bit half of the last block, not yet consumed
   uint64_t next64() {
     if (has_spare) { has_spare = false; return spare; }
@@ -40,7 +33,7 @@ struct HostRng {
   }
   double gaussian(double mean, double sigma) {
     uint64_t a = next64(), b = next64();
-    double u1 = ((double)(a >> 11) + 1.0) * 0x1.0p-53, u2 = (double)(b >> 11) * 0x1.0p-53;
+    double u1 = to_oc(a), u2 = to_co(b);
     return mean + sigma * (std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586476925 * u2));
   }
 };

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/emat_host.h"
+#include "emat_gamma_pure.hpp"     // the generator the site-rate moves' key is drawn from
 #include "flat_tree.hpp"
 #include "host_parallel.hpp"
 #include "synth.hpp"
@@ -47,6 +48,7 @@ struct RunDriver {
   // model
   bool have_hky = false; double hky_mu = 0, hky_kappa = 1, hky_pi[4] = {0.25, 0.25, 0.25, 0.25};
   std::vector<double> nu_l;
+  bool site_rate_moves_on = false; double site_rate_alpha = 1.0; uint64_t site_rate_rounds = 0;   // Run::alpha_ and how many rounds of site-rate moves have drawn a key
   bool have_pop = false; emat_pop_model pop{}; std::vector<double> sky_x, sky_g;
   double t_step = 1.0; bool t_step_set = false;
   int only_displacing_inner_nodes = 0, topology_moves_enabled = 1;
@@ -414,7 +416,33 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // One cycle after another (run.cpp:622-657 minus global moves)
+  // Run::alpha_moves + gibbs_sample_all_nus (run.cpp:1105-1235) on the device, from the statistics the device computes.
+  static constexpr const char* kShardedStatistics = "a sharded run gathers the part lengths and sums S, R across ranks itself (see emat_backend.h)";
+  static constexpr uint64_t kSiteRateKeyTag = 0x5349544552415445ull;   // "SITERATE"
+  emat_status Ttwiddle_ext(const double* tree_length_of_part, int32_t* ext_offset, int32_t* ext_node, double* ext_length, int32_t capacity, int32_t* count);   // (both below, with the tree of parts)
+  emat_status get_Ttwiddle_l(double* Ttwiddle_l);
+  emat_status site_rate_moves(emat_site_rate_result* out) {
+    EMAT_TRY(need_backend());
+    EMAT_TRY(need_parts_out());
+    if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
+    std::vector<double> Tt((size_t)L); std::vector<int32_t> M((size_t)L);
+    EMAT_TRY(get_Ttwiddle_l(Tt.data()));
+    EMAT_TRY(bk(emat_get_num_muts_l(backend, M.data())));
+    uint32_t w[4]; philox4x32_10_pure(site_rate_rounds, seed ^ kSiteRateKeyTag, w);
+    const uint64_t key = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    emat_site_rate_result res{};
+    if (out) { res.trace = out->trace; res.trace_capacity = out->trace_capacity; }
+    EMAT_TRY(bk(emat_site_rate_moves(backend, Tt.data(), M.data(), site_rate_alpha, 10 /* run.cpp:1193 */, key, &res)));
+    ++site_rate_rounds;
+    // the backend holds the new rates already; kept here so that the next push sends the same values
+    site_rate_alpha = res.alpha;
+    nu_l.resize((size_t)L);
+    EMAT_TRY(bk(emat_get_nu_l(backend, nu_l.data())));
+    if (out) *out = res;
+    return EMAT_OK;
+  }
+
+  // One cycle after another (run.cpp:622-657; of the global moves, the site-rate group when it is on)
   emat_status do_mcmc_steps(int64_t steps, int64_t per_cycle) {
     EMAT_TRY(need_backend());
     if (shard_world > 1) return fail(EMAT_ERR_STATE, "a sharded run is cycled by its caller, who owns the collectives (see emat_host.h)");
@@ -423,6 +451,7 @@ struct RunDriver {
       HostLaps laps(verbose_reports());
       EMAT_TRY(repartition());
       laps.lap(); laps.mark("cycle: 1 repartition");
+      if (site_rate_moves_on) EMAT_TRY(site_rate_moves(nullptr));   // where the reference runs its global moves (run.cpp:635-641)
       const int64_t k = std::min(per_cycle, steps - done);
       EMAT_TRY(run_moves(k));
       if (paranoid) EMAT_TRY(bk(emat_check_derived(backend, 1.0, nullptr, nullptr)));
@@ -644,9 +673,9 @@ emat_status emat_run_moves_sharded(emat_run* r, int64_t count) {   // Run::run_l
 }
 // For calc_Ttwiddle_l: the whole-tree branch length hanging below every boundary tip of the LOCAL parts, from the lengths
 // inside every part of the run and the tree of parts (a part's boundary tips are the cut nodes of the parts below it).
-emat_status emat_run_Ttwiddle_ext(emat_run* r, const double* tree_length_of_part, int32_t* ext_offset, int32_t* ext_node, double* ext_length, int32_t capacity, int32_t* count) {
-  if (!r || !tree_length_of_part || !ext_offset || !count || capacity < 0 || (capacity > 0 && (!ext_node || !ext_length))) return EMAT_ERR_INVALID_ARGUMENT;
-  RunDriver& d = r->d;
+}  // extern "C"
+emat_status emat::RunDriver::Ttwiddle_ext(const double* tree_length_of_part, int32_t* ext_offset, int32_t* ext_node, double* ext_length, int32_t capacity, int32_t* count) {
+  RunDriver& d = *this;
   EMAT_TRY(d.ensure_partition_on_host());
   const int P = (int)d.parts.size();
   if (P == 0 || (int)d.part_kids.size() != P) return d.fail(EMAT_ERR_STATE, "repartition first");
@@ -677,20 +706,37 @@ emat_status emat_run_Ttwiddle_ext(emat_run* r, const double* tree_length_of_part
   return n <= capacity ? EMAT_OK : d.fail(EMAT_ERR_BUFFER_TOO_SMALL, "emat_run_Ttwiddle_ext: arrays too small");
 }
 // calc_Ttwiddle_l of the whole tree from the parts on the device (single process).
-emat_status emat_run_get_Ttwiddle_l(emat_run* r, double* Ttwiddle_l) {
-  if (!r || !Ttwiddle_l) return EMAT_ERR_INVALID_ARGUMENT;
-  RunDriver& d = r->d;
+emat_status emat::RunDriver::get_Ttwiddle_l(double* Ttwiddle_l) {
+  RunDriver& d = *this;
   EMAT_TRY(d.need_backend());
   EMAT_TRY(d.need_parts_out());
-  if (d.shard_world > 1) return d.fail(EMAT_ERR_STATE, "a sharded run gathers the part lengths and sums S, R across ranks itself (see emat_backend.h)");
+  if (d.shard_world > 1) return d.fail(EMAT_ERR_STATE, RunDriver::kShardedStatistics);
   const int P = (int)d.parts.size();
   std::vector<double> len(P);
   EMAT_TRY(d.bk(emat_get_part_tree_lengths(d.backend, len.data())));
   std::vector<int32_t> off(P + 1), node(P); std::vector<double> val(P); int32_t cnt = 0;
-  EMAT_TRY(emat_run_Ttwiddle_ext(r, len.data(), off.data(), node.data(), val.data(), P, &cnt));
+  EMAT_TRY(Ttwiddle_ext(len.data(), off.data(), node.data(), val.data(), P, &cnt));
   std::vector<double> S(d.L), R(d.L); double T = 0.0;
   EMAT_TRY(d.bk(emat_Ttwiddle_l_partial(d.backend, off.data(), node.data(), val.data(), S.data(), R.data(), &T)));
   return d.bk(emat_Ttwiddle_l_finish(d.backend, S.data(), R.data(), T, Ttwiddle_l));
+}
+extern "C" {
+emat_status emat_run_Ttwiddle_ext(emat_run* r, const double* tree_length_of_part, int32_t* ext_offset, int32_t* ext_node, double* ext_length, int32_t capacity, int32_t* count) {
+  if (!r || !tree_length_of_part || !ext_offset || !count || capacity < 0 || (capacity > 0 && (!ext_node || !ext_length))) return EMAT_ERR_INVALID_ARGUMENT;
+  return r->d.Ttwiddle_ext(tree_length_of_part, ext_offset, ext_node, ext_length, capacity, count);
+}
+emat_status emat_run_get_Ttwiddle_l(emat_run* r, double* Ttwiddle_l) { if (!r || !Ttwiddle_l) return EMAT_ERR_INVALID_ARGUMENT; return r->d.get_Ttwiddle_l(Ttwiddle_l); }
+emat_status emat_run_set_site_rate_moves(emat_run* r, int32_t on, double alpha) {
+  if (!r || !std::isfinite(alpha) || !(alpha > 0.0)) return EMAT_ERR_INVALID_ARGUMENT;
+  r->d.site_rate_moves_on = on != 0; r->d.site_rate_alpha = alpha;
+  return EMAT_OK;
+}
+emat_status emat_run_site_rate_moves(emat_run* r, emat_site_rate_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.site_rate_moves(out); }
+emat_status emat_run_get_site_rates(emat_run* r, double* alpha, double* nu_l) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (alpha) *alpha = r->d.site_rate_alpha;
+  if (nu_l) { if (r->d.nu_l.empty()) std::fill(nu_l, nu_l + r->d.L, 1.0); else std::copy(r->d.nu_l.begin(), r->d.nu_l.end(), nu_l); }
+  return EMAT_OK;
 }
 
 emat_status emat_run_pack_local_parts(emat_run* r, uint8_t* buf, uint64_t capacity, uint64_t* bytes_needed) {

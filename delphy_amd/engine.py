@@ -89,6 +89,47 @@ class _SamplesProbeResultC(C.Structure):
                 ("order_stats", C.POINTER(C.c_double)), ("cells_to_skip", C.POINTER(C.c_int32))]
 
 
+class _SiteRateStepC(C.Structure):
+    _fields_ = [("proposed_alpha", C.c_double), ("log_p_proposed", C.c_double), ("log_metropolis", C.c_double), ("u", C.c_double), ("accepted", C.c_int32), ("pad_", C.c_int32)]
+
+
+class _SiteRateResultC(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("log_p_alpha_start", C.c_double), ("num_accepted", C.c_int32), ("num_floored", C.c_int32),
+                ("delta_log_G", C.c_double), ("delta_log_prior_alpha", C.c_double), ("delta_log_prior_nu", C.c_double),
+                ("sum_nu_old", C.c_double), ("sum_nu_new", C.c_double), ("trace", C.POINTER(_SiteRateStepC)), ("trace_capacity", C.c_int32)]
+
+
+SITE_RATE_STEP_DTYPE = np.dtype([("proposed_alpha", "f8"), ("log_p_proposed", "f8"), ("log_metropolis", "f8"), ("u", "f8"), ("accepted", "i4"), ("pad_", "i4")])
+
+
+@dataclass
+class SiteRateResult:
+    """What emat_site_rate_moves returns (include/emat_backend.h: emat_site_rate_result)."""
+    alpha: float                   # alpha after the steps
+    log_p_alpha_start: float       # log p(alpha) at the alpha passed in
+    num_accepted: int
+    num_floored: int
+    delta_log_G: float
+    delta_log_prior_alpha: float
+    delta_log_prior_nu: float
+    sum_nu_old: float
+    sum_nu_new: float
+    trace: Optional[np.ndarray]    # [num_alpha_steps] records of SITE_RATE_STEP_DTYPE, or None when not asked for
+
+    @staticmethod
+    def _of(res: "_SiteRateResultC", trace):
+        return SiteRateResult(res.alpha, res.log_p_alpha_start, res.num_accepted, res.num_floored, res.delta_log_G, res.delta_log_prior_alpha,
+                              res.delta_log_prior_nu, res.sum_nu_old, res.sum_nu_new, trace)
+
+
+def _site_rate_result_c(num_steps: int, trace: bool):
+    res = _SiteRateResultC()
+    tr = np.zeros(max(1, num_steps), SITE_RATE_STEP_DTYPE) if trace else None
+    if trace:
+        res.trace = tr.ctypes.data_as(C.POINTER(_SiteRateStepC)); res.trace_capacity = num_steps
+    return res, tr
+
+
 @dataclass
 class SamplesProbe:
     """What emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors return (include/emat_backend.h: emat_samples_probe_result).
@@ -368,6 +409,8 @@ def load_library():
         "emat_tree_samples_probe_site_states": [B, P(_PopModelC), i32, i32, i32, i32, i32, P(i32), dbl, dbl, i32, P(_SamplesProbeResultC)],
         "emat_mcc_probe_site_states": [B, P(_PopModelC), i32, i32, P(i32), dbl, dbl, i32, P(_SamplesProbeResultC)],
         "emat_run_note_device_reassembled": [R, i32, P(i32), P(C.c_uint8)], "emat_run_set_paranoid": [R, i32], "emat_run_set_reference_remainder": [R, i32],
+        "emat_site_rate_moves": [B, P(dbl), P(i32), dbl, i32, u64, P(_SiteRateResultC)], "emat_get_nu_l": [B, P(dbl)], "emat_debug_sample_gamma": [B, u64, i32, dbl, dbl, P(dbl)],
+        "emat_run_set_site_rate_moves": [R, i32, dbl], "emat_run_site_rate_moves": [R, P(_SiteRateResultC)], "emat_run_get_site_rates": [R, P(dbl), P(dbl)],
     }
     M = C.c_void_p
     sigs.update({
@@ -1028,6 +1071,28 @@ class EmatBackend:
             out.append([[int(m[1]), int(m[0]), int(m[2]), float(m[3])] for m in muts[k: k + counts[i]]]); k += int(counts[i])
         return out
 
+    def site_rate_moves(self, Ttwiddle_l, num_muts_l, alpha: float, num_alpha_steps: int = 10, key: int = 0, trace: bool = True) -> "SiteRateResult":
+        """alpha_moves + gibbs_sample_all_nus on the device (include/emat_backend.h: emat_site_rate_moves), from the run's summed statistics."""
+        T = np.ascontiguousarray(Ttwiddle_l, np.float64); M = np.ascontiguousarray(num_muts_l, np.int32)
+        if T.shape != (self.num_sites,) or M.shape != (self.num_sites,):
+            raise ValueError("Ttwiddle_l and num_muts_l must have one entry per site")
+        res, tr = _site_rate_result_c(int(num_alpha_steps), trace and num_alpha_steps > 0)
+        self._ck(self._lib.emat_site_rate_moves(self._h, T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int32)), float(alpha), int(num_alpha_steps),
+                                                int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_site_rate_moves")
+        return SiteRateResult._of(res, None if tr is None else tr[:num_alpha_steps])
+
+    def nu_l(self) -> np.ndarray:
+        """The handle's relative site rates: what set_evo was given, or the last site-rate move's draws."""
+        out = np.zeros(self.num_sites)
+        self._ck(self._lib.emat_get_nu_l(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "emat_get_nu_l")
+        return out
+
+    def debug_sample_gamma(self, key: int, n: int, shape: float, rate: float) -> np.ndarray:
+        """Test hook: n draws of the site-rate moves' gamma sampler, draw i from the stream (key, i)."""
+        out = np.zeros(max(0, int(n)))
+        self._ck(self._lib.emat_debug_sample_gamma(self._h, int(key) & 0xFFFFFFFFFFFFFFFF, int(n), float(shape), float(rate), out.ctypes.data_as(C.POINTER(C.c_double))), "emat_debug_sample_gamma")
+        return out
+
     def debug_gamma(self, mode: int, a, x_or_q) -> np.ndarray:
         """Test hook: the device's gamma_q (mode 0) / gamma_q_inv (mode 1), point by point."""
         a = np.ascontiguousarray(a, np.float64); x = np.ascontiguousarray(x_or_q, np.float64); out = np.zeros_like(a)
@@ -1248,6 +1313,22 @@ class EmatRun:
 
     def reassemble(self):
         self._ck(self._lib.emat_run_reassemble(self._h), "emat_run_reassemble")
+
+    def set_site_rate_moves(self, on: bool = True, alpha: float = 1.0):
+        """Site-rate moves once per cycle of do_mcmc_steps (off by default); `alpha` is where the steps start (reference default 1.0)."""
+        self._ck(self._lib.emat_run_set_site_rate_moves(self._h, 1 if on else 0, float(alpha)), "emat_run_set_site_rate_moves")
+
+    def site_rate_moves(self, trace: bool = False) -> "SiteRateResult":
+        """One round of site-rate moves while the parts are out (emat_run_site_rate_moves): ten alpha steps and the draw of every nu_l."""
+        res, tr = _site_rate_result_c(10, trace)
+        self._ck(self._lib.emat_run_site_rate_moves(self._h, C.byref(res)), "emat_run_site_rate_moves")
+        return SiteRateResult._of(res, tr)
+
+    def site_rates(self):
+        """(alpha, nu_l) as the driver holds them."""
+        a = C.c_double(); nu = np.zeros(self.num_sites)
+        self._ck(self._lib.emat_run_get_site_rates(self._h, C.byref(a), nu.ctypes.data_as(C.POINTER(C.c_double))), "emat_run_get_site_rates")
+        return a.value, nu
 
     def Ttwiddle_l(self) -> np.ndarray:
         """calc_Ttwiddle_l of the whole tree, computed from the parts on the device (single process)."""

@@ -557,6 +557,48 @@ emat_status emat_Ttwiddle_l_partial(emat_backend* h, const int32_t* ext_offset, 
                                     double* S /*[num_sites]*/, double* R /*[num_sites]*/, double* tree_length_below_root /* may be NULL */);
 emat_status emat_Ttwiddle_l_finish(emat_backend* h, const double* S_sum, const double* R_sum, double tree_length, double* Ttwiddle_l /*[num_sites]*/);
 
+/* ---- the site-rate moves: steps on alpha, then a Gibbs draw of every nu_l --------------------------------------------------
+ * replaces: Run::alpha_moves and Run::gibbs_sample_all_nus (reference run.cpp:1105-1235), the one group of global moves whose work
+ * grows with the number of sites: `num_alpha_steps` scaling Metropolis steps on the shape alpha of the site-rate prior (scale
+ * uniform in [0.9, 1/0.9), exponential prior of mean 1, target calc_log_p_alpha, :1157-1215), the increment of the alpha prior
+ * from the rates as they were (:1218-1231), and nu_l ~ Gamma(M_l + alpha, rate mu_l Ttwiddle_l + alpha) for every site, floored
+ * at 1e-50 (:1114-1151), with the increments of log G and of the nu prior.  All on the device, in three launches.
+ *
+ * Inputs are the statistics of the WHOLE run, as SUMS over all handles: Ttwiddle_l from emat_Ttwiddle_l_finish and the summed
+ * vectors of emat_get_num_muts_l (a sharded caller all-reduces both as it already does for Ttwiddle_l).  Random numbers come from
+ * streams named by (key, site) -- block j of site l is Philox4x32-10 of counter (l << 32) | j under `key`; the alpha steps use the
+ * pseudo-site 0xFFFFFFFF, step s taking block s: word 0 the scale, word 1 the acceptance uniform, drawn whether needed or not --
+ * and every sum is added in a fixed order: with the same evolution model, the same arguments give the same nu_l and the same
+ * result BIT FOR BIT on every handle and in every call.
+ *
+ * The call first finishes a pending pass (which reads the rates).  Afterwards the handle's nu_l are the new ones, as if given to
+ * emat_set_evo: the parts' derived quantities are stale and are recomputed by the next run or by emat_recalc_derived.
+ * `out->trace` (may be NULL) receives one record per step; `trace_capacity` is its room.
+ * EMAT_ERR_INVALID_ARGUMENT (text in emat_last_error, naming the first offending site where there is one): a null pointer, alpha
+ * not finite or <= 0, num_alpha_steps < 0, trace_capacity < num_alpha_steps with a trace, a Ttwiddle_l that is negative or not
+ * finite, a negative count -- all answered before the device is asked for.  EMAT_ERR_NO_DEVICE: a handle without a device (there
+ * is no CPU path).  EMAT_ERR_STATE: before emat_set_evo.  After any refusal nu_l is untouched and the next call works.
+ *
+ *   emat_get_nu_l             the handle's relative site rates: what emat_set_evo was given, or the last move's draws
+ *   emat_debug_sample_gamma   test hook: n draws of the moves' sampler (Marsaglia-Tsang; a shape below 1 drawn at shape + 1 and
+ *                             multiplied by u^(1 / shape); no floor), draw i from the stream (key, i) */
+typedef struct emat_site_rate_step { double proposed_alpha, log_p_proposed, log_metropolis, u; int32_t accepted, pad_; } emat_site_rate_step;
+typedef struct emat_site_rate_result {
+  double alpha;                    /* out: alpha after the steps */
+  double log_p_alpha_start;        /* out: log p(alpha) at the alpha passed in */
+  int32_t num_accepted, num_floored;
+  double delta_log_G;              /* run.cpp:1144 summed over the sites */
+  double delta_log_prior_alpha;    /* run.cpp:1226-1231 */
+  double delta_log_prior_nu;       /* run.cpp:1148 + 1151 */
+  double sum_nu_old, sum_nu_new;
+  emat_site_rate_step* trace; int32_t trace_capacity;   /* may be NULL / 0 */
+} emat_site_rate_result;
+emat_status emat_site_rate_moves(emat_backend* h, const double* Ttwiddle_l /*[L]*/, const int32_t* num_muts_l /*[L]*/,
+                                 double alpha, int32_t num_alpha_steps /* 10 in the reference; 0 = gibbs_sample_all_nus alone */,
+                                 uint64_t key, emat_site_rate_result* out);
+emat_status emat_get_nu_l(emat_backend* h, double* nu_l /*[L]*/);
+emat_status emat_debug_sample_gamma(emat_backend* h, uint64_t key, int32_t n, double shape, double rate, double* out /*[n]*/);  /* draw i uses stream (key, i) */
+
 /* replaces: Run::calc_cur_log_coalescent_prior (reference run.cpp:455-465), i.e. Scalable_coalescent_prior::calc_log_prior
  * (scalable_coalescent.cpp:163-187) with every node displaced to its current time (:88-138): the whole-tree grid prior
  *   - sum_cells t_step kbar (kbar - 1) / (2 Nbar)  -  sum over inner nodes of log N(t),

@@ -11,7 +11,9 @@
  *   Run::run_local_moves (run.cpp:682-693)                 emat_run_moves        -> emat_run_moves_even of the backend (remainder spread over the parts)
  *   Run::reassemble (run.cpp:195-256)                      emat_run_reassemble
  *   Run::do_mcmc_steps without the global moves            emat_run_do_mcmc_steps
- *     (run.cpp:622-657; global moves are out of scope)
+ *     (run.cpp:622-657; of the global moves only the site-rate group is built)
+ *   Run::alpha_moves, gibbs_sample_all_nus                 emat_run_site_rate_moves  -> emat_site_rate_moves of the backend
+ *     (run.cpp:1105-1235)
  *
  * Also exports the seeded synthetic-EMAT generator used by the bench and the tests
  * (SURVEY section 8(d) configs C1..C5).
@@ -197,7 +199,23 @@ emat_status emat_run_get_Ttwiddle_l(emat_run* r, double* Ttwiddle_l /*[num_sites
 emat_status emat_run_Ttwiddle_ext(emat_run* r, const double* tree_length_of_part /*[all parts of the run]*/, int32_t* ext_offset /*[local parts + 1]*/,
                                   int32_t* ext_node, double* ext_length, int32_t capacity, int32_t* count);
 
-/* repartition -> [push params, local moves, reassemble] per cycle of `local_moves_per_cycle` moves
+/* The site-rate moves in the run (reference Run::alpha_moves + gibbs_sample_all_nus, run.cpp:1105-1235; engine call:
+ * emat_site_rate_moves of emat_backend.h).  Off by default: a run without them keeps the nu_l of emat_run_set_hky.
+ *   emat_run_set_site_rate_moves  on / off, and the alpha the steps start from (the reference's default is 1.0; finite, > 0).
+ *   emat_run_site_rate_moves      one round while the parts are out, like emat_run_get_Ttwiddle_l: Ttwiddle_l as that call computes
+ *                                 it, the mutations per site (emat_get_num_muts_l), ten alpha steps and the draw of every nu_l, with
+ *                                 key = the first 64-bit word of Philox4x32-10(counter = rounds so far, key = run seed ^ a fixed tag).
+ *                                 alpha and nu_l are kept in the driver, so that the next emat_run_push_params sends the same
+ *                                 values.  `out` may be NULL.  A sharded run gets EMAT_ERR_STATE: its caller owns the collectives
+ *                                 and calls the engine itself with the summed statistics.
+ *   emat_run_get_site_rates       alpha and nu_l as the driver holds them (either pointer may be NULL).
+ * With the moves on, emat_run_do_mcmc_steps does one round per cycle where the reference runs its global moves: after the
+ * repartition and before the cycle's local moves (run.cpp:635-641).  With them off the cycle is what it was. */
+emat_status emat_run_set_site_rate_moves(emat_run* r, int32_t on, double alpha /* start value, reference default 1.0 */);
+emat_status emat_run_site_rate_moves(emat_run* r, emat_site_rate_result* out /* may be NULL */);   /* needs the parts out, like emat_run_get_Ttwiddle_l */
+emat_status emat_run_get_site_rates(emat_run* r, double* alpha, double* nu_l /* either may be NULL */);
+
+/* repartition -> [push params, site-rate moves when on, local moves, reassemble] per cycle of `local_moves_per_cycle` moves
  * (<= 0: 50 x nodes, the reference default run.cpp:669-672), repartitioning at every cycle boundary. */
 emat_status emat_run_do_mcmc_steps(emat_run* r, int64_t steps, int64_t local_moves_per_cycle);
 
