@@ -14,6 +14,8 @@ from .engine import (  # noqa: F401
     MccTree,
     PopModel,
     SamplesProbe,
+    SkygridMovesResult,
+    SkygridSpec,
     SynthParams,
     TipDescs,
     build_library,

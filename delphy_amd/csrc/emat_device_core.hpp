@@ -892,6 +892,58 @@ EMAT_DN double skygrid_log_int_N(const PopTable& p, double a, double b) {   // p
   }
   return m_log(result) + bias;
 }
+// The gradient of the Skygrid curve with respect to one knot value, what the population moves' force is made of
+// (emat_skygrid_kernels.hpp).  d log N(t) / d gamma_k: pop_model.cpp:206-225.
+EMAT_D double skygrid_d_log_N_d_gamma(const PopTable& p, double t, int k) {
+  const double* x = p.skygrid_x;
+  const int kk = skygrid_interval(p, t), M = p.skygrid_num_knots - 1;
+  if (kk == 0) return k == 0 ? 1.0 : 0.0;
+  if (kk > M) return k == M ? 1.0 : 0.0;
+  if (p.skygrid_type == 1) return k == kk ? 1.0 : 0.0;
+  const double cc = (t - x[kk - 1]) / (x[kk] - x[kk - 1]);
+  return k == kk - 1 ? 1 - cc : (k == kk ? cc : 0.0);
+}
+// d log(integral of N over [a, b]) / d gamma_kp: pop_model.cpp:333-523 with gamma_eff = gamma, in its order of operations -- its
+// bias, its series for |Delta| < 1e-5 (which also replaces expm1(Delta) / Delta in the integral by 1 + Delta / 2) and its J(+-Delta).
+// J is only formed for the two pieces that touch knot kp: the other pieces never read it.  a == b gives 0 / 0 as there.
+EMAT_D double skygrid_d_log_int_N_d_gamma(const PopTable& p, double a, double b, int kp) {
+  const double* x = p.skygrid_x; const double* ge = p.skygrid_gamma;
+  const int M = p.skygrid_num_knots - 1;
+  const int ka = skygrid_interval(p, a), kb = skygrid_interval(p, b);
+  const int kka = ka - 1 > 0 ? ka - 1 : 0, kkb = kb < M ? kb : M;
+  double bias = -k_inf;
+  for (int k = kka; k <= kkb; ++k) bias = bias > ge[k] ? bias : ge[k];
+  double biased_int = 0.0, biased_deriv = 0.0;
+  for (int k = ka; k <= kb; ++k) {
+    const double lo = k > 0 ? (a > x[k - 1] ? a : x[k - 1]) : a;
+    const double hi = k <= M ? (b < x[k] ? b : x[k]) : b;
+    if (k == 0 || k == M + 1 || p.skygrid_type == 1) {
+      const int kg = k == 0 ? 0 : (k == M + 1 ? M : k);
+      const double piece = m_exp(-bias + ge[kg]) * (hi - lo);
+      biased_int += piece;
+      biased_deriv += kp == kg ? piece : 0.0;
+      continue;
+    }
+    const double c_lo = (lo - x[k - 1]) / (x[k] - x[k - 1]), c_hi = (hi - x[k - 1]) / (x[k] - x[k - 1]);
+    const double G_lo = (1 - c_lo) * ge[k - 1] + c_lo * ge[k], G_hi = (1 - c_hi) * ge[k - 1] + c_hi * ge[k];
+    const double D = G_hi - G_lo;
+    const bool series = __builtin_fabs(D) < 1e-5;
+    const double e_lo = m_exp(-bias + G_lo);
+    if (series) biased_int += e_lo * (hi - lo) * (1 + 0.5 * D);
+    else biased_int += e_lo * (hi - lo) * (m_expm1(D) / D);
+    if (kp != k && kp != k - 1) continue;
+    double J_plus, J_minus;
+    if (series) { J_plus = 0.5 + D / 3; J_minus = 0.5 - D / 3; }
+    else {
+      J_plus = (+D * m_exp(+D) - m_expm1(+D)) / (D * D);
+      J_minus = (-D * m_exp(-D) - m_expm1(-D)) / (D * D);
+    }
+    const double e_hi = m_exp(-bias + G_hi);
+    if (kp == k) biased_deriv += (hi - lo) * (c_hi * e_lo * J_plus + c_lo * e_hi * J_minus);
+    else biased_deriv += (hi - lo) * ((1 - c_hi) * e_lo * J_plus + (1 - c_lo) * e_hi * J_minus);
+  }
+  return biased_deriv / biased_int;
+}
 EMAT_NOTAIL EMAT_DN double pop_integral(const PopTable& p, double a, double b) {
   if (p.kind == 0) return (b - a) * p.p[0];
   if (p.kind == 1) {   // pop_model.cpp:43-91

@@ -50,6 +50,7 @@ struct RunDriver {
   std::vector<double> nu_l;
   bool site_rate_moves_on = false; double site_rate_alpha = 1.0; uint64_t site_rate_rounds = 0;   // Run::alpha_ and how many rounds of site-rate moves have drawn a key
   bool have_pop = false; emat_pop_model pop{}; std::vector<double> sky_x, sky_g;
+  bool skygrid_moves_on = false; emat_skygrid_spec sky_spec{}; uint64_t skygrid_rounds = 0;   // Run's Skygrid settings with skygrid_tau_, and how many rounds of the Skygrid moves have drawn a key
   double t_step = 1.0; bool t_step_set = false;
   int only_displacing_inner_nodes = 0, topology_moves_enabled = 1;
   bool reference_remainder = false;   // the remainder of count / parts goes to part 0 as in Run::run_local_moves (run.cpp:683-689), instead of one move per part
@@ -76,6 +77,7 @@ struct RunDriver {
   bool device_tree_uploaded = false;   // device_tree: the tree has gone to the device
   bool host_tree_stale = false;        // device_tree: the device's tree has moved on since `tree` was last brought up to date
   bool partition_on_device = false;    // the current partition was made by emat_tree_partition: parts[p].orig / part_kids are filled on demand
+  bool tree_cut = false;               // between a repartition and the reassemble that follows it: the parts, not `tree` / the tree in HBM, hold the state (a host tree's parts stay uploaded after it)
   void model_changed() { model_pushed = false; }                 // HKY parameters, flags, or the reference sequence (hence cum_Q)
   void model_went_out() { model_pushed = true; }
   void pop_model_changed() { coal_built = false; }
@@ -362,7 +364,9 @@ struct RunDriver {
     build_subtrees(tree, ref, parts, part_kids, states, subtrees);
     draw_part_seeds();
   }
-  emat_status repartition() {   // run.cpp:110-193 (+ refresh_partition_stencils :87-108)
+  emat_status repartition() { emat_status st = repartition_(); if (st == EMAT_OK) tree_cut = true; return st; }
+  emat_status reassemble() { emat_status st = reassemble_(); if (st == EMAT_OK) tree_cut = false; return st; }
+  emat_status repartition_() {   // run.cpp:110-193 (+ refresh_partition_stencils :87-108)
     if (device_tree) return repartition_device();
     HostLaps laps(verbose_reports());
     parts_cut(false);
@@ -398,7 +402,7 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  emat_status reassemble() {   // run.cpp:195-256
+  emat_status reassemble_() {   // run.cpp:195-256
     if (device_tree) return reassemble_device();
     HostLaps laps(verbose_reports());
     try {
@@ -442,13 +446,64 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // One cycle after another (run.cpp:622-657; of the global moves, the site-rate group when it is on)
+  // Run::skygrid_tau_move + skygrid_gammas_zero_mode_gibbs_move + skygrid_gammas_hmc_move (run.cpp:766-778) on the device, on the ASSEMBLED tree: from
+  // the tree in HBM where it lives there, else from the two statistics made here from the host's tree (scalable_coalescent.cpp:88-138).
+  static constexpr uint64_t kSkygridKeyTag = 0x534B594752494431ull;   // "SKYGRID1"
+  void host_tree_coalescent_stats(double t_ref, double ts, int32_t& first_cell, std::vector<double>& k_bar, std::vector<double>& inner_t) const {
+    const auto cell = [&](double t) { return (int64_t)std::floor((t - t_ref) / ts); };
+    double t_last = -INFINITY;
+    for (auto& n : tree.nodes) if (n.is_tip() && n.t > t_last) t_last = n.t;
+    const int64_t c0 = cell(tree.nodes[tree.root].t), c1 = std::max(c0, cell(t_last));
+    first_cell = (int32_t)c0; k_bar.assign((size_t)(c1 - c0 + 1), 0.0); inner_t.clear();
+    const auto add = [&](double a, int64_t cs, double b) {   // add_interval(a, b, +1), :88-116
+      int64_t ce = std::min(std::max(cell(b), c0), c1); cs = std::min(std::max(cs, c0), c1);
+      if (cs == ce) { k_bar[(size_t)(cs - c0)] += (b - a) / ts; return; }
+      k_bar[(size_t)(cs - c0)] += ((t_ref + (double)(cs + 1) * ts) - a) / ts;
+      k_bar[(size_t)(ce - c0)] += (b - (t_ref + (double)ce * ts)) / ts;
+      for (int64_t c = cs + 1; c < ce; ++c) k_bar[(size_t)(c - c0)] += 1.0;
+    };
+    for (size_t v = 0; v < tree.nodes.size(); ++v) {
+      const HNode& n = tree.nodes[v];
+      if (!n.is_tip()) inner_t.push_back(n.t);
+      if ((int)v == tree.root) add(t_ref + (double)c0 * ts, c0, n.t);   // one lineage before the root inside its cell (:56)
+      else if (n.parent != EMAT_NO_NODE) add(tree.nodes[(size_t)n.parent].t, cell(tree.nodes[(size_t)n.parent].t), n.t);
+    }
+  }
+  emat_status skygrid_moves(emat_skygrid_result* out) {
+    EMAT_TRY(need_backend());
+    if (tree_cut) return fail(EMAT_ERR_STATE, "the Skygrid moves need the tree assembled: reassemble first");
+    if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
+    EMAT_TRY(need_pop_model());
+    if (pop.kind != EMAT_POP_SKYGRID) return fail(EMAT_ERR_INVALID_ARGUMENT, "the Skygrid moves need a Skygrid population model");
+    uint32_t w[4]; philox4x32_10_pure(skygrid_rounds, seed ^ kSkygridKeyTag, w);
+    const uint64_t key = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    std::vector<double> gamma(sky_g.size());
+    emat_skygrid_result res{};
+    res.gamma = gamma.data();
+    if (out) { res.trace = out->trace; res.trace_capacity = out->trace_capacity; }
+    const emat_pop_model pm = pop_view();
+    const double t_ref = tree.t_max_tip(), ts = coalescent_step();
+    if (device_tree && device_tree_uploaded) EMAT_TRY(bk(emat_tree_skygrid_moves(backend, &pm, &sky_spec, t_ref, ts, key, &res)));
+    else {
+      int32_t first_cell = 0; std::vector<double> k_bar, inner_t;
+      host_tree_coalescent_stats(t_ref, ts, first_cell, k_bar, inner_t);
+      EMAT_TRY(bk(emat_skygrid_moves(backend, &pm, &sky_spec, t_ref, ts, first_cell, (int32_t)k_bar.size(), k_bar.data(), (int32_t)inner_t.size(), inner_t.data(), key, &res)));
+    }
+    ++skygrid_rounds;
+    sky_g = gamma; sky_spec.tau = res.tau;
+    pop_model_changed();
+    if (out) { double* user_gamma = out->gamma; *out = res; out->gamma = user_gamma; if (user_gamma) std::copy(gamma.begin(), gamma.end(), user_gamma); }
+    return EMAT_OK;
+  }
+
+  // One cycle after another (run.cpp:622-657; of the global moves, the site-rate and the Skygrid groups when they are on)
   emat_status do_mcmc_steps(int64_t steps, int64_t per_cycle) {
     EMAT_TRY(need_backend());
     if (shard_world > 1) return fail(EMAT_ERR_STATE, "a sharded run is cycled by its caller, who owns the collectives (see emat_host.h)");
     if (per_cycle <= 0) per_cycle = 50 * (int64_t)tree.nodes.size();
     for (int64_t done = 0; done < steps;) {
       HostLaps laps(verbose_reports());
+      if (skygrid_moves_on) EMAT_TRY(skygrid_moves(nullptr));   // on the whole tree, BEFORE the repartition, which then builds the parts' tables from the new curve (emat_host.h)
       EMAT_TRY(repartition());
       laps.lap(); laps.mark("cycle: 1 repartition");
       if (site_rate_moves_on) EMAT_TRY(site_rate_moves(nullptr));   // where the reference runs its global moves (run.cpp:635-641)
@@ -576,7 +631,7 @@ emat_status emat_run_note_device_reassembled(emat_run* r, int32_t num_root_delta
   d.device_parts_came_back();
   return EMAT_OK;
 }
-emat_status emat_run_repartition(emat_run* r) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.repartition(); }
+emat_status emat_run_repartition(emat_run* r) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.repartition(); }   // (sets tree_cut)
 emat_status emat_run_num_parts(emat_run* r, int32_t* n, int32_t* root_part) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; if (n) *n = (int)r->d.parts.size(); if (root_part) *root_part = r->d.root_part; return EMAT_OK; }
 emat_status emat_run_part_sizes(emat_run* r, int32_t p, int32_t* nn, int32_t* nm, int32_t* ni, int32_t* nf) {
   if (r && r->d.device_tree) return r->d.fail(EMAT_ERR_STATE, "with a device-resident tree the parts exist only on the device (emat_part_get_sizes / emat_part_download of the backend)");
@@ -732,6 +787,25 @@ emat_status emat_run_set_site_rate_moves(emat_run* r, int32_t on, double alpha) 
   return EMAT_OK;
 }
 emat_status emat_run_site_rate_moves(emat_run* r, emat_site_rate_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.site_rate_moves(out); }
+emat_status emat_run_set_skygrid_moves(emat_run* r, int32_t on, const emat_skygrid_spec* spec) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!spec) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_skygrid_moves: spec must not be null");
+  const emat_skygrid_spec& s = *spec;
+  if (!std::isfinite(s.tau) || !(s.tau > 0.0)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_skygrid_moves: tau must be finite and positive");
+  if (s.low_gamma_barrier_enabled && (!std::isfinite(s.low_gamma_barrier_scale) || !(s.low_gamma_barrier_scale > 0.0)))
+    return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_skygrid_moves: low_gamma_barrier_scale must be finite and positive with the barrier on");
+  if (s.hmc_steps < 0 || !std::isfinite(s.hmc_mean_dt) || !(s.hmc_mean_dt > 0.0)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_skygrid_moves: hmc_steps must not be negative and hmc_mean_dt must be finite and positive");
+  r->d.skygrid_moves_on = on != 0; r->d.sky_spec = s;
+  return EMAT_OK;
+}
+emat_status emat_run_skygrid_moves(emat_run* r, emat_skygrid_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.skygrid_moves(out); }
+emat_status emat_run_get_skygrid(emat_run* r, double* gamma, double* tau) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!r->d.have_pop || r->d.pop.kind != EMAT_POP_SKYGRID) return r->d.fail(EMAT_ERR_STATE, "emat_run_get_skygrid: the run has no Skygrid population model");
+  if (gamma) std::copy(r->d.sky_g.begin(), r->d.sky_g.end(), gamma);
+  if (tau) *tau = r->d.sky_spec.tau;
+  return EMAT_OK;
+}
 emat_status emat_run_get_site_rates(emat_run* r, double* alpha, double* nu_l) {
   if (!r) return EMAT_ERR_INVALID_ARGUMENT;
   if (alpha) *alpha = r->d.site_rate_alpha;

@@ -128,6 +128,14 @@ struct GTreeHost {
   GPools pools() { GPools q{}; q.muts = pool_muts.p; q.ivs = pool_ivs.p; q.mut_cap = (uint32_t)pool_muts.n; q.iv_cap = (uint32_t)pool_ivs.n; q.tops = pool_tops.p; return q; }
 };
 
+// What the Skygrid population moves work in (emat_skygrid_kernels.hpp, emat_skygrid_host.hpp): grow-only, kept from call to call.  k_bar, inner_t and the
+// grid's numbers are also where emat_tree_coalescent_stats leaves the tree's statistics for emat_tree_skygrid_moves.
+struct SkygridScratch {
+  DevBuf<double> x, g, k_bar, popsize_bar, inner_t, c, W, gamma_out, result, trace, extent;
+  DevBuf<int32_t> count;
+  int32_t first_cell = 0, num_cells = 0, num_inner = 0;
+};
+
 // Scratch of the tree probers (emat_probe_kernels.hpp, emat_probe_host.hpp): allocated at the first call, grown on demand.
 struct ProbeScratch {
   DevBuf<int32_t> val, jump_a, jump_b, marked, diff, status;
@@ -267,6 +275,7 @@ struct emat_backend {
   DevBuf<uint8_t> d_headers; std::vector<uint8_t> h_headers; bool headers_current = false;
   GTreeHost gt;                     // the whole tree, when it lives in HBM (emat_tree_upload)
   ProbeScratch probe;               // what emat_tree_probe_* / emat_tree_branch_counts work in
+  SkygridScratch sky;               // what emat_skygrid_moves / emat_tree_coalescent_stats work in
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
   int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs

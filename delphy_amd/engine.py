@@ -7,6 +7,7 @@ file:line of every entry point.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 from dataclasses import dataclass, field
@@ -128,6 +129,78 @@ def _site_rate_result_c(num_steps: int, trace: bool):
     if trace:
         res.trace = tr.ctypes.data_as(C.POINTER(_SiteRateStepC)); res.trace_capacity = num_steps
     return res, tr
+
+
+class _SkygridSpecC(C.Structure):
+    _fields_ = [("tau", C.c_double), ("tau_move_enabled", C.c_int32), ("low_gamma_barrier_enabled", C.c_int32),
+                ("tau_prior_alpha", C.c_double), ("tau_prior_beta", C.c_double), ("low_gamma_barrier_loc", C.c_double), ("low_gamma_barrier_scale", C.c_double),
+                ("inv_nbar_prior_alpha", C.c_double), ("inv_nbar_prior_beta", C.c_double),
+                ("do_tau", C.c_int32), ("do_zero_mode", C.c_int32), ("do_hmc", C.c_int32), ("hmc_steps", C.c_int32), ("hmc_mean_dt", C.c_double)]
+
+
+_SKYGRID_RESULT_DOUBLES_1 = ("tau", "log_coalescent_prior_start", "log_coalescent_prior_end", "delta_log_other_priors", "tau_post_alpha", "tau_post_beta", "tau_draw",
+                             "tau_delta_log_prior", "zero_B", "zero_shape", "zero_rate", "zero_I_bar", "zero_delta_gamma_bar", "zero_log_metropolis", "zero_u")
+_SKYGRID_RESULT_DOUBLES_2 = ("hmc_dt", "hmc_K_old", "hmc_K_new", "hmc_U_prior_old", "hmc_U_prior_new", "hmc_U_coal_old", "hmc_U_coal_new", "hmc_log_metropolis", "hmc_u")
+_SKYGRID_RESULT_INTS_1 = ("zero_accepted", "hmc_accepted")
+_SKYGRID_RESULT_INTS_2 = ("hmc_K_exit_step", "hmc_nan", "hmc_steps_done")
+
+
+class _SkygridResultC(C.Structure):
+    _fields_ = ([("gamma", C.POINTER(C.c_double))] + [(f, C.c_double) for f in _SKYGRID_RESULT_DOUBLES_1] + [(f, C.c_int32) for f in _SKYGRID_RESULT_INTS_1] +
+                [(f, C.c_double) for f in _SKYGRID_RESULT_DOUBLES_2] + [(f, C.c_int32) for f in _SKYGRID_RESULT_INTS_2] +
+                [("trace_capacity", C.c_int32), ("trace", C.POINTER(C.c_double))])
+
+
+@dataclass
+class SkygridSpec:
+    """The settings of the Skygrid population moves (include/emat_backend.h: emat_skygrid_spec); the defaults are the reference's."""
+    tau: float = 1.0
+    tau_move_enabled: bool = True
+    low_gamma_barrier_enabled: bool = False
+    tau_prior_alpha: float = 0.001
+    tau_prior_beta: float = 0.001
+    low_gamma_barrier_loc: float = 0.0
+    low_gamma_barrier_scale: float = -math.log(0.70)
+    inv_nbar_prior_alpha: float = 0.0
+    inv_nbar_prior_beta: float = 0.0
+    do_tau: bool = True
+    do_zero_mode: bool = True
+    do_hmc: bool = True
+    hmc_steps: int = 25
+    hmc_mean_dt: float = 2.0 * math.pi / 100.0
+
+    def c_struct(self) -> "_SkygridSpecC":
+        return _SkygridSpecC(float(self.tau), int(self.tau_move_enabled), int(self.low_gamma_barrier_enabled), float(self.tau_prior_alpha), float(self.tau_prior_beta),
+                             float(self.low_gamma_barrier_loc), float(self.low_gamma_barrier_scale), float(self.inv_nbar_prior_alpha), float(self.inv_nbar_prior_beta),
+                             int(self.do_tau), int(self.do_zero_mode), int(self.do_hmc), int(self.hmc_steps), float(self.hmc_mean_dt))
+
+
+class SkygridMovesResult:
+    """What emat_skygrid_moves returns (include/emat_backend.h: emat_skygrid_result): `gamma` [knots], every scalar of the result under
+    its header name, and -- when asked for -- the trace taken apart: c_k, W_k, m_k, gamma_hmc_start, p_initial [knots] and, per leapfrog
+    step made, gamma_half, f, p, gamma_after [hmc_steps_done][knots]."""
+
+    def __init__(self, res: "_SkygridResultC", gamma: np.ndarray, trace):
+        self.gamma = gamma
+        for f in _SKYGRID_RESULT_DOUBLES_1 + _SKYGRID_RESULT_DOUBLES_2:
+            setattr(self, f, float(getattr(res, f)))
+        for f in _SKYGRID_RESULT_INTS_1 + _SKYGRID_RESULT_INTS_2:
+            setattr(self, f, int(getattr(res, f)))
+        self.trace = trace
+        if trace is not None:
+            self.c_k, self.W_k, self.m_k, self.gamma_hmc_start, self.p_initial = trace[:5]
+            steps = trace[5: 5 + 4 * self.hmc_steps_done].reshape(self.hmc_steps_done, 4, trace.shape[1])
+            self.gamma_half, self.f, self.p, self.gamma_after = steps[:, 0], steps[:, 1], steps[:, 2], steps[:, 3]
+
+
+def _skygrid_result_c(num_knots: int, hmc_steps: int, trace: bool):
+    """(the C result with room for the curve and, when asked for, the trace; the two arrays)."""
+    dp = C.POINTER(C.c_double)
+    gamma = np.zeros(max(1, num_knots)); res = _SkygridResultC(); res.gamma = gamma.ctypes.data_as(dp)
+    tr = np.zeros((5 + 4 * max(0, int(hmc_steps)), max(1, num_knots))) if trace else None
+    if trace:
+        res.trace = tr.ctypes.data_as(dp); res.trace_capacity = max(0, int(hmc_steps))
+    return res, gamma, tr
 
 
 @dataclass
@@ -410,6 +483,11 @@ def load_library():
         "emat_mcc_probe_site_states": [B, P(_PopModelC), i32, i32, P(i32), dbl, dbl, i32, P(_SamplesProbeResultC)],
         "emat_run_note_device_reassembled": [R, i32, P(i32), P(C.c_uint8)], "emat_run_set_paranoid": [R, i32], "emat_run_set_reference_remainder": [R, i32],
         "emat_site_rate_moves": [B, P(dbl), P(i32), dbl, i32, u64, P(_SiteRateResultC)], "emat_get_nu_l": [B, P(dbl)], "emat_debug_sample_gamma": [B, u64, i32, dbl, dbl, P(dbl)],
+        "emat_skygrid_moves": [B, P(_PopModelC), P(_SkygridSpecC), dbl, dbl, i32, i32, P(dbl), i32, P(dbl), u64, P(_SkygridResultC)],
+        "emat_debug_pop_gradient": [B, P(_PopModelC), i32, i32, i32, P(dbl), P(dbl), P(dbl)],
+        "emat_tree_coalescent_stats": [B, dbl, dbl, P(i32), P(i32), P(dbl), i32, P(dbl), i32, P(i32)],
+        "emat_tree_skygrid_moves": [B, P(_PopModelC), P(_SkygridSpecC), dbl, dbl, u64, P(_SkygridResultC)],
+        "emat_run_set_skygrid_moves": [R, i32, P(_SkygridSpecC)], "emat_run_skygrid_moves": [R, P(_SkygridResultC)], "emat_run_get_skygrid": [R, P(dbl), P(dbl)],
         "emat_run_set_site_rate_moves": [R, i32, dbl], "emat_run_site_rate_moves": [R, P(_SiteRateResultC)], "emat_run_get_site_rates": [R, P(dbl), P(dbl)],
     }
     M = C.c_void_p
@@ -1081,6 +1159,40 @@ class EmatBackend:
                                                 int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_site_rate_moves")
         return SiteRateResult._of(res, None if tr is None else tr[:num_alpha_steps])
 
+    def skygrid_moves(self, pop: PopModel, spec: "SkygridSpec", t_ref: float, t_step: float, first_cell: int, k_bar, inner_t, key: int = 0, trace: bool = False) -> "SkygridMovesResult":
+        """skygrid_tau_move + the zero mode's Gibbs move + the HMC on the gammas, on the device (include/emat_backend.h: emat_skygrid_moves), from the
+        run's statistics: the lineage grid k_bar over the cells first_cell .. and the inner nodes' times."""
+        kb = np.ascontiguousarray(k_bar, np.float64).reshape(-1); ts = np.ascontiguousarray(inner_t, np.float64).reshape(-1)
+        m = pop.c_struct(); sp = spec.c_struct(); n = int(m.skygrid_num_knots); dp = C.POINTER(C.c_double)
+        res, gamma, tr = _skygrid_result_c(n, spec.hmc_steps, trace)
+        self._ck(self._lib.emat_skygrid_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(first_cell), kb.shape[0], kb.ctypes.data_as(dp),
+                                              ts.shape[0], ts.ctypes.data_as(dp), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_skygrid_moves")
+        return SkygridMovesResult(res, gamma[:n], tr)
+
+    def tree_coalescent_stats(self, t_ref: float, t_step: float):
+        """(first_cell, k_bar, inner_t) of the tree resident in HBM (emat_tree_coalescent_stats): Scalable_coalescent_prior's whole-tree grid over the
+        cells from the root's to the latest tip's, and the inner nodes' times in node order."""
+        fc, nc, ni = C.c_int32(), C.c_int32(), C.c_int32(); dp = C.POINTER(C.c_double)
+        self._ck(self._lib.emat_tree_coalescent_stats(self._h, float(t_ref), float(t_step), C.byref(fc), C.byref(nc), None, 0, None, 0, C.byref(ni)), "emat_tree_coalescent_stats")
+        kb = np.zeros(max(1, nc.value)); ts = np.zeros(max(1, ni.value))
+        self._ck(self._lib.emat_tree_coalescent_stats(self._h, float(t_ref), float(t_step), C.byref(fc), C.byref(nc), kb.ctypes.data_as(dp), kb.shape[0], ts.ctypes.data_as(dp), ts.shape[0], C.byref(ni)),
+                 "emat_tree_coalescent_stats")
+        return fc.value, kb[: nc.value], ts[: ni.value]
+
+    def tree_skygrid_moves(self, pop: PopModel, spec: "SkygridSpec", t_ref: float, t_step: float, key: int = 0, trace: bool = False) -> "SkygridMovesResult":
+        """emat_skygrid_moves on the statistics of the tree resident in HBM, which never leave it (emat_tree_skygrid_moves)."""
+        m = pop.c_struct(); sp = spec.c_struct(); n = int(m.skygrid_num_knots)
+        res, gamma, tr = _skygrid_result_c(n, spec.hmc_steps, trace)
+        self._ck(self._lib.emat_tree_skygrid_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_tree_skygrid_moves")
+        return SkygridMovesResult(res, gamma[:n], tr)
+
+    def debug_pop_gradient(self, pop: PopModel, op: int, k: int, a, b) -> np.ndarray:
+        """Test hook: the device's d log(integral of N over [a, b]) / d gamma_k (op 3) / d log N(a) / d gamma_k (op 4), point by point."""
+        a = np.ascontiguousarray(a, np.float64); b = np.ascontiguousarray(b, np.float64); out = np.zeros_like(a)
+        m = pop.c_struct(); dp = C.POINTER(C.c_double)
+        self._ck(self._lib.emat_debug_pop_gradient(self._h, C.byref(m), int(op), int(k), a.shape[0], a.ctypes.data_as(dp), b.ctypes.data_as(dp), out.ctypes.data_as(dp)), "emat_debug_pop_gradient")
+        return out
+
     def nu_l(self) -> np.ndarray:
         """The handle's relative site rates: what set_evo was given, or the last site-rate move's draws."""
         out = np.zeros(self.num_sites)
@@ -1269,6 +1381,7 @@ class EmatRun:
     def set_pop_model(self, pop: PopModel):
         m = pop.c_struct()
         self._ck(self._lib.emat_run_set_pop_model(self._h, C.byref(m)), "emat_run_set_pop_model")
+        self._sky_knots = int(m.skygrid_num_knots) if pop.kind == 2 else 0
 
     def set_coalescent_t_step(self, t_step: float):
         self._ck(self._lib.emat_run_set_coalescent_t_step(self._h, t_step), "emat_run_set_coalescent_t_step")
@@ -1323,6 +1436,25 @@ class EmatRun:
         res, tr = _site_rate_result_c(10, trace)
         self._ck(self._lib.emat_run_site_rate_moves(self._h, C.byref(res)), "emat_run_site_rate_moves")
         return SiteRateResult._of(res, tr)
+
+    def set_skygrid_moves(self, on: bool = True, spec: "SkygridSpec" = None):
+        """The Skygrid population moves once per cycle of do_mcmc_steps, before the repartition (off by default); `spec`: Run's Skygrid settings and the tau to start from."""
+        sp = (spec or SkygridSpec()).c_struct()
+        self._ck(self._lib.emat_run_set_skygrid_moves(self._h, 1 if on else 0, C.byref(sp)), "emat_run_set_skygrid_moves")
+        self._sky_steps = int(sp.hmc_steps)
+
+    def skygrid_moves(self, trace: bool = False) -> "SkygridMovesResult":
+        """One round of the Skygrid moves on the assembled tree (emat_run_skygrid_moves): tau, the zero mode, the HMC on the gammas."""
+        n = getattr(self, "_sky_knots", 0)
+        res, gamma, tr = _skygrid_result_c(n, getattr(self, "_sky_steps", 25), trace)
+        self._ck(self._lib.emat_run_skygrid_moves(self._h, C.byref(res)), "emat_run_skygrid_moves")
+        return SkygridMovesResult(res, gamma[:n], tr)
+
+    def skygrid(self):
+        """(gamma, tau) of the Skygrid curve as the driver holds them."""
+        g = np.zeros(max(1, getattr(self, "_sky_knots", 0))); tau = C.c_double()
+        self._ck(self._lib.emat_run_get_skygrid(self._h, g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(tau)), "emat_run_get_skygrid")
+        return g[: getattr(self, "_sky_knots", 0)], tau.value
 
     def site_rates(self):
         """(alpha, nu_l) as the driver holds them."""

@@ -599,6 +599,100 @@ emat_status emat_site_rate_moves(emat_backend* h, const double* Ttwiddle_l /*[L]
 emat_status emat_get_nu_l(emat_backend* h, double* nu_l /*[L]*/);
 emat_status emat_debug_sample_gamma(emat_backend* h, uint64_t key, int32_t n, double shape, double rate, double* out /*[n]*/);  /* draw i uses stream (key, i) */
 
+/* ---- the Skygrid population moves: tau, the zero mode and the HMC on the gammas ----------------------------------------------
+ * replaces: the Skygrid branch of Run::run_global_moves (reference run.cpp:766-778): skygrid_tau_move (:1321-1358),
+ * skygrid_gammas_zero_mode_gibbs_move (:2016-2189) and skygrid_gammas_hmc_move (:1360-2014), in that order, on the device in two
+ * launches (csrc/emat_skygrid_kernels.hpp): the inner nodes' statistics per knot, then ONE workgroup for the three moves and every
+ * leapfrog step.
+ *
+ * Inputs are the statistics of the WHOLE run as host arrays: the lineage grid of Scalable_coalescent_prior
+ * (scalable_coalescent.cpp:88-138), k_bar[c] for the cells j = first_cell .. first_cell + num_cells - 1, cell j = [t_ref + j t_step,
+ * t_ref + (j + 1) t_step) as emat_scalable_coalescent_partial numbers them (1 lineage before the root inside the root's cell), and
+ * the times of the inner nodes (any order; the sums over them are added in the order given).  A sharded caller adds the grids
+ * and concatenates the times.  `pop_model` is the Skygrid curve the moves start from.
+ *
+ * Random numbers: the (key, id) streams of the site-rate moves.  Knot k's initial momentum is sqrt(m_k) x one Box-Muller normal,
+ * the first two words of stream (key, k).  Five pseudo-ids at the top of the range, each drawn from its stream's start and drawn
+ * whether needed or not:
+ *   0xFFFFFFFE  the tau draw (Marsaglia-Tsang, as emat_debug_sample_gamma)    0xFFFFFFFD  the zero mode's I_bar draw (same sampler)
+ *   0xFFFFFFFC  the zero mode's acceptance uniform, [0, 1)                     0xFFFFFFFB  dt = -hmc_mean_dt log(u), u in (0, 1]
+ *   0xFFFFFFFA  the HMC's acceptance uniform, [0, 1)
+ * Every sum is added in a fixed order and there are no atomics: the same arguments give the same result BIT FOR BIT on every handle and
+ * in every call.  The sum over inner nodes of log N(t_i) is formed as sum_k W_k gamma_k, W_k = sum_i d log N(t_i) / d gamma_k (log N is
+ * linear in the gammas for both Skygrid types), so the nodes are read once per call.
+ *
+ * The call first finishes a pending pass.  It changes nothing in the handle: the caller hands the new curve to the next
+ * emat_tree_repartition / emat_build_coalescent_parts.
+ * EMAT_ERR_INVALID_ARGUMENT (text in emat_last_error naming the first offender), all answered before the device is asked for: a null
+ * pointer; a model that is not a Skygrid or that the model check refuses; t_ref not finite or t_step not finite and positive; tau not
+ * finite or <= 0; a barrier scale <= 0 (or not finite) with the barrier on; hmc_steps < 0; hmc_mean_dt not finite or <= 0; num_cells < 1;
+ * num_inner < 1; a k_bar that is negative or not finite; an inner_t that is not finite or lies outside the grid's cells; a trace
+ * with trace_capacity < hmc_steps.  EMAT_ERR_CAPACITY: more than 1 024 knots or 2^22 cells, or cell numbers outside [-2^30, 2^30).  EMAT_ERR_NO_DEVICE: a handle without
+ * a device, after the argument checks (there is no CPU path).
+ *
+ *   emat_debug_pop_gradient   test hook: the device's gradient of the Skygrid curve, point by point (reference pop_model.cpp:206-225,
+ *                             333-523).  op 3: out[i] = d log(integral of N over [a[i], b[i]]) / d gamma_k; op 4: out[i] =
+ *                             d log N(a[i]) / d gamma_k.  (emat_debug_pop's ops 0-2 and signature are as they were.) */
+typedef struct emat_skygrid_spec {          /* Run's setters, reference run.h:85-91 and neighbours */
+  double tau;                                /* in: skygrid_tau_ */
+  int32_t tau_move_enabled, low_gamma_barrier_enabled;
+  double tau_prior_alpha, tau_prior_beta;
+  double low_gamma_barrier_loc, low_gamma_barrier_scale;
+  double inv_nbar_prior_alpha, inv_nbar_prior_beta;
+  int32_t do_tau, do_zero_mode, do_hmc;      /* which of the three to run, in the reference's order (tau also needs tau_move_enabled) */
+  int32_t hmc_steps;                         /* 25 in the reference */
+  double hmc_mean_dt;                        /* 2 pi / 100 in the reference */
+} emat_skygrid_spec;
+typedef struct emat_skygrid_result {
+  double* gamma;                             /* out [num_knots], the caller's array: the curve after the three moves */
+  double tau;                                /* after the tau move (the tau passed in when it did not run) */
+  double log_coalescent_prior_start;         /* calc_log_prior, scalable_coalescent.cpp:163-187, under the model passed in */
+  double log_coalescent_prior_end;           /* ... under the model returned (run.cpp:2170, :2004) */
+  double delta_log_other_priors;             /* run.cpp:1355-1357 + :2186-2187 + :2005, of the moves that ran and were accepted */
+  /* skygrid_tau_move */
+  double tau_post_alpha, tau_post_beta;      /* run.cpp:1343-1344 */
+  double tau_draw;                           /* :1352; drawn also when the move does not run */
+  double tau_delta_log_prior;                /* :1355-1357; 0 when it did not run */
+  /* skygrid_gammas_zero_mode_gibbs_move */
+  double zero_B;                             /* run.cpp:2108-2112 */
+  double zero_shape, zero_rate;              /* :2115-2117 */
+  double zero_I_bar;                         /* :2120, the draw */
+  double zero_delta_gamma_bar;               /* :2121 */
+  double zero_log_metropolis, zero_u;        /* :2164-2165; u in [0, 1) */
+  int32_t zero_accepted;
+  /* skygrid_gammas_hmc_move */
+  int32_t hmc_accepted;                      /* run.cpp:1994 */
+  double hmc_dt;                             /* :1885 */
+  double hmc_K_old, hmc_K_new;               /* :1855, :1973 (new = old when the move ended early or did not run) */
+  double hmc_U_prior_old, hmc_U_prior_new;   /* :1856, :1974 */
+  double hmc_U_coal_old, hmc_U_coal_new;     /* :1857, :1975 */
+  double hmc_log_metropolis, hmc_u;          /* :1978, :1994; u in [0, 1) */
+  int32_t hmc_K_exit_step;                   /* the K > 100 (M + 1) rule: -1 = it never ended the move, 0 = the initial momenta (:1868), s >= 1 = after
+                                                the momentum update of leapfrog step s, counted from 1 (:1940) */
+  int32_t hmc_nan;                           /* :1981-1989 ended it */
+  int32_t hmc_steps_done;                    /* force evaluations made */
+  int32_t trace_capacity;                    /* in: leapfrog steps `trace` has room for (>= hmc_steps) */
+  /* may be NULL: [5 + 4 * trace_capacity][num_knots] doubles.  Rows 0-4: c_k (run.cpp:1695-1702), W_k, m_k (:1708), gamma at the start of
+   * the HMC, the initial p_k (:1852).  Then four rows per leapfrog step made: gamma after the first half step (:1893-1895), f_k (:1900),
+   * p_k after the momentum step (:1931-1933), gamma after the second half step (:1950-1952; the half-step gamma again where the K rule
+   * ended the move at this step). */
+  double* trace;
+} emat_skygrid_result;
+emat_status emat_skygrid_moves(emat_backend* h, const emat_pop_model* pop_model, const emat_skygrid_spec* spec, double t_ref, double t_step,
+                               int32_t first_cell, int32_t num_cells, const double* k_bar /*[num_cells]*/,
+                               int32_t num_inner, const double* inner_t /*[num_inner]*/, uint64_t key, emat_skygrid_result* out);
+/* The statistics emat_skygrid_moves reads, from the tree resident in HBM as it stands after emat_tree_upload / emat_tree_reassemble (EMAT_ERR_STATE
+ * while the parts are out, as the tree probers): the reference's whole-tree grid (Scalable_coalescent_prior, scalable_coalescent.cpp:88-138), k_bar[c]
+ * over the cells from the root's to the latest tip's with 1 lineage before the root inside the root's cell, and the times of the inner nodes in node
+ * order.  With null k_bar / inner_t only the sizes are returned; EMAT_ERR_BUFFER_TOO_SMALL when an array given is too short.  Cell c is one workgroup
+ * adding the branches in a fixed order, no atomics: the same bits from call to call.  The arrays also stay in buffers of the handle, and
+ * emat_tree_skygrid_moves is emat_skygrid_moves on them without their leaving HBM: bit for bit what emat_skygrid_moves returns when fed the
+ * arrays this call hands out.  Its refusals are emat_skygrid_moves' own, then the tree's state. */
+emat_status emat_tree_coalescent_stats(emat_backend* h, double t_ref, double t_step, int32_t* first_cell, int32_t* num_cells, double* k_bar /*[k_bar_capacity] or NULL*/,
+                                       int32_t k_bar_capacity, double* inner_t /*[inner_capacity] or NULL*/, int32_t inner_capacity, int32_t* num_inner);
+emat_status emat_tree_skygrid_moves(emat_backend* h, const emat_pop_model* pop_model, const emat_skygrid_spec* spec, double t_ref, double t_step, uint64_t key, emat_skygrid_result* out);
+emat_status emat_debug_pop_gradient(emat_backend* h, const emat_pop_model* pop_model, int32_t op, int32_t k, int32_t n, const double* a, const double* b, double* out);
+
 /* replaces: Run::calc_cur_log_coalescent_prior (reference run.cpp:455-465), i.e. Scalable_coalescent_prior::calc_log_prior
  * (scalable_coalescent.cpp:163-187) with every node displaced to its current time (:88-138): the whole-tree grid prior
  *   - sum_cells t_step kbar (kbar - 1) / (2 Nbar)  -  sum over inner nodes of log N(t),

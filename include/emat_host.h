@@ -215,6 +215,26 @@ emat_status emat_run_set_site_rate_moves(emat_run* r, int32_t on, double alpha /
 emat_status emat_run_site_rate_moves(emat_run* r, emat_site_rate_result* out /* may be NULL */);   /* needs the parts out, like emat_run_get_Ttwiddle_l */
 emat_status emat_run_get_site_rates(emat_run* r, double* alpha, double* nu_l /* either may be NULL */);
 
+/* The Skygrid population moves of a run (Run::skygrid_tau_move, skygrid_gammas_zero_mode_gibbs_move, skygrid_gammas_hmc_move, reference
+ * run.cpp:766-778; emat_skygrid_moves / emat_tree_skygrid_moves of emat_backend.h).  Off by default: a run without them keeps the curve of
+ * emat_run_set_pop_model for ever, and its cycle's code path is what it was.
+ *   emat_run_set_skygrid_moves  on / off, and Run's Skygrid settings with the tau to start from (EMAT_ERR_INVALID_ARGUMENT: what
+ *                               emat_skygrid_moves refuses in a spec).
+ *   emat_run_skygrid_moves      one round on the ASSEMBLED tree -- EMAT_ERR_STATE while the parts are out, the opposite of
+ *                               emat_run_site_rate_moves.  With the tree in HBM: emat_tree_skygrid_moves, the statistics never leave the device;
+ *                               with the tree on the host: the lineage grid and the coalescence times made from it here, then emat_skygrid_moves.
+ *                               t_ref is the latest tip bound (calc_max_tip_time), t_step the coalescent step of the parts.  The key of round k is
+ *                               the first word of Philox(counter k, key = run seed ^ a fixed tag), as for the site rates.  The accepted curve and
+ *                               tau become the run's, and the next repartition builds the parts' coalescent tables from them.  `out` (may be NULL):
+ *                               out->gamma and out->trace may each be NULL.  A sharded run is refused as the site-rate moves refuse it.
+ *   emat_run_get_skygrid        the curve's gammas and tau as the run holds them (either pointer may be NULL).
+ * With the group on, emat_run_do_mcmc_steps does one round at the top of every cycle, BEFORE the repartition.  The reference runs its
+ * global moves on the whole tree right after ITS repartition and rebuilds the parts' coalescent tables afterwards (run.cpp:635-647,
+ * :267-275); this driver's repartition builds those tables itself, so moving first gives the parts the new curve in one build. */
+emat_status emat_run_set_skygrid_moves(emat_run* r, int32_t on, const emat_skygrid_spec* spec);
+emat_status emat_run_skygrid_moves(emat_run* r, emat_skygrid_result* out /* may be NULL */);   /* needs the tree assembled */
+emat_status emat_run_get_skygrid(emat_run* r, double* gamma /*[knots]*/, double* tau /* either may be NULL */);
+
 /* repartition -> [push params, site-rate moves when on, local moves, reassemble] per cycle of `local_moves_per_cycle` moves
  * (<= 0: 50 x nodes, the reference default run.cpp:669-672), repartitioning at every cycle boundary. */
 emat_status emat_run_do_mcmc_steps(emat_run* r, int64_t steps, int64_t local_moves_per_cycle);
