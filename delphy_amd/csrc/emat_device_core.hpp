@@ -117,6 +117,13 @@ template <class T> EMAT_DF const EMAT_CONST_AS T* uniform_const_ptr(const T* p) 
   return (const EMAT_CONST_AS T*)(((uint64_t)hi << 32) | lo);
 }
 
+// One lane runs the chain, so a value its loop branches on is the same in every active lane -- which LLVM cannot know of a value read
+// from memory or returned by a call: it lowers such a branch as divergent, with exit and continue masks kept in SGPR pairs, merged with
+// exec at every join and, the moves saving no registers, parked in VGPR lanes across every move call.  Said where the value is loaded
+// or returned, the branch is s_cmp / s_cbranch_scc.  Only for what every active lane agrees on.
+EMAT_DF uint32_t uniform_u32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+EMAT_DF bool uniform_flag(bool b) { return __builtin_amdgcn_ballot_w64(b) != 0ull; }   // (the compare's own lane mask, tested whole: no select + readfirstlane)
+
 // ---- per-wave context ----------------------------------------------------------------------------
 struct Ctx {
   uint8_t* S;                 // slab base (LDS or HBM; generic address space)
@@ -306,6 +313,8 @@ EMAT_D double u01_oo(Ctx& c) { return to_oo(rng_next64(c)); }
 EMAT_D double u01_oc(Ctx& c) { return to_oc(rng_next64(c)); }
 EMAT_D double uniform_co(Ctx& c, double lo, double hi) { return lo + (hi - lo) * u01_co(c); }
 EMAT_D double uniform_oc(Ctx& c, double lo, double hi) { return lo + (hi - lo) * u01_oc(c); }
+// floor(x n / 2^64) of the next word x, for n >= 1 (every caller: a node count, a list length, 3).  The sign-extended n costs four
+// multiplies where (uint32_t)n would take two; that spelling measured inside the run-to-run spread and was not kept.
 EMAT_D int uniform_int(Ctx& c, int n) { return (int)__umul64hi(rng_next64(c), (uint64_t)n); }
 EMAT_D double gaussian(Ctx& c, double mean, double sigma) {
   uint64_t a = rng_next64(c), b = rng_next64(c);

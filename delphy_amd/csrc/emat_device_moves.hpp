@@ -642,11 +642,13 @@ template <bool kRoot> EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
 #ifdef EMAT_PROFILE_PHASES
   const long long _mv0 = clock64();
 #endif
-  if (c.phase == 1) spr1_move_propose(c);
-  else if (c.phase == 2) spr1_move_finish(c);
+  // (what the frame branches on is said to be uniform where it is loaded or returned: uniform_flag, emat_device_core.hpp)
+  const uint32_t phase = uniform_u32(c.phase);
+  if (phase == 1) spr1_move_propose(c);
+  else if (phase == 2) spr1_move_finish(c);
   else {
   // space check BEFORE the move, so that a stop leaves a consistent state
-  if (hdr_of(c)->heap_top > c.heap_limit) { if (!make_heap_room(c)) return false; }
+  if (uniform_flag(hdr_of(c)->heap_top > c.heap_limit)) { if (!uniform_flag(make_heap_room(c))) return false; }
   sc_reset(c);
   if (kRoot) c.mv_rng_pos = c.rng_pos;
   if (c.only_displacing_inner_nodes) inner_node_displace_move<kRoot>(c);
@@ -662,17 +664,17 @@ template <bool kRoot> EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
 #ifdef EMAT_PROFILE_PHASES
   { const long long _dt = clock64() - _mv0; hdr_of(c)->phase_ticks[(c.tr_kind >= 3) ? 15 : 14] += _dt; if (c.tr_kind == 0) EMAT_COUNT(c, 10, _dt); else if (c.tr_kind == 1) EMAT_COUNT(c, 15, _dt); }   // (inner-node / tip displacements apart: reserved[10], [15])
 #endif
-  if (c.svc != 0 && !c.failed) return true;   // parked: the move is not over
+  if (uniform_u32(c.svc) != 0 && !uniform_flag(c.failed)) return true;   // parked: the move is not over
   c.phase = 0; c.svc = 0;
-  if (hdr_of(c)->status == k_part_need_cells) return false;   // stopped before the move changed anything (stop_for_cells): not a move
-  if (hdr_of(c)->trace_len < hdr_of(c)->trace_cap) {
+  if (uniform_flag(hdr_of(c)->status == k_part_need_cells)) return false;   // stopped before the move changed anything (stop_for_cells): not a move
+  if (uniform_flag(hdr_of(c)->trace_len < hdr_of(c)->trace_cap)) {
     double* tr = (double*)slab_at(c, hdr_of(c)->off_trace) + 4 * hdr_of(c)->trace_len;
     const bool noted = c.tr_acc >= 0;
     tr[0] = (double)c.tr_kind; tr[1] = (double)c.tr_node; tr[2] = noted ? (double)c.tr_acc : 0.0; tr[3] = noted ? c.tr_log_mh : __builtin_nan("");
     hdr_of(c)->trace_len++;
   }
   hdr_of(c)->moves_done++;
-  return !c.failed;
+  return !uniform_flag(c.failed);
 }
 
 // The chain itself: `c.moves_left` sub-iterations.  Its own function, and its counter in the context, so that nothing is
@@ -683,13 +685,13 @@ template <bool kRoot> EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
 template <bool kRoot> EMAT_NOTAIL EMAT_DN void run_chain(Ctx& c) {
   c.svc = 0;
   for (;;) {
-    if (c.phase == 0) {
-      if (c.moves_left <= 0) return;
-      if (rng_wants_fill(c)) { c.svc = 2; return; }                 // the wave computes the next stretch of the stream (rng_fill), then calls again
+    if (uniform_u32(c.phase) == 0) {
+      if (uniform_flag(c.moves_left <= 0)) return;
+      if (uniform_flag(rng_wants_fill(c))) { c.svc = 2; return; }   // the wave computes the next stretch of the stream (rng_fill), then calls again
       c.moves_left -= 1;
     }
-    if (!mcmc_sub_iteration<kRoot>(c)) { c.moves_left = 0; c.phase = 0; c.svc = 0; return; }
-    if (c.svc != 0) return;
+    if (!uniform_flag(mcmc_sub_iteration<kRoot>(c))) { c.moves_left = 0; c.phase = 0; c.svc = 0; return; }
+    if (uniform_u32(c.svc) != 0) return;
   }
 }
 // The one place that asks which kind of part this is: the loop and the three simple moves below it are compiled for each.
