@@ -332,6 +332,7 @@ class OracleBuild:
             self.L._build_sigs = True
         ref = np.ascontiguousarray(ref, np.uint8)
         self.num_sites = int(ref.shape[0])
+        self.ref = ref
         self.h = E()
         assert self.L.orc_build_create(_ptr(ref, C.c_uint8), ref.shape[0], C.byref(self.h)) == 0
 

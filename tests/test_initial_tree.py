@@ -8,30 +8,9 @@ import numpy as np
 import pytest
 
 import delphy_amd as d
+from builder_cases import FIELDS, build_both
 from delphy_amd.scenarios import make_scenario
 from oracle_ffi import OracleBuild
-
-FIELDS = ("parent", "child0", "child1", "t", "t_min", "t_max", "mut_offset", "mut_site", "mut_from", "mut_to", "mut_t",
-          "miss_offset", "miss_start", "miss_end", "mfs_offset", "mfs_site", "mfs_state")
-
-
-def build_both(sc, seed):
-    ob = OracleBuild(sc.ref)
-    tips = ob.tip_descs_of(sc.tree)
-    b = d.EmatBackend(sc.num_sites)
-    try:
-        b.set_ref_sequence(sc.ref)
-        got = b.build_usher_like(tips, seed)
-        want = ob.build_usher_like(tips, seed)
-        assert got.root == want.root
-        for f in FIELDS:
-            x, y = getattr(got, f), getattr(want, f)
-            assert x.shape == y.shape and np.array_equal(x, y), "%s differs (seed %d)" % (f, seed)
-        rc, msg = ob.check(got, tips)
-        assert rc == 0, msg
-        return got, tips
-    finally:
-        b.close(); ob.close()
 
 
 @pytest.mark.gpu
