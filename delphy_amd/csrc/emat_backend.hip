@@ -31,9 +31,8 @@
 #include "host_parallel.hpp"
 #include "emat_gtree_kernels.hpp"   // the whole tree in HBM: cutting it into part slabs and gathering the parts back
 #include "emat_build.hpp"           // initial-tree construction: the graft loop as a kernel, the finishing passes on the host
-#include "emat_probe_kernels.hpp"   // the tree probers on the resident tree: lineage and site-state prevalence over time
+#include "emat_probe_kernels.hpp"   // the tree probers, one family for the resident tree and the kept samples: lineage and site-state prevalence over time
 #include "emat_mcc_kernels.hpp"     // sampled trees kept in HBM, and the maximum-clade-credibility tree derived from them
-#include "emat_samples_probe_kernels.hpp"   // the ancestral prober over many sampled trees at once, mean and order statistics of its answers
 #include "emat_site_rate_kernels.hpp"   // the site-rate moves: steps on alpha and the Gibbs draw of every nu_l
 #include "emat_skygrid_kernels.hpp"     // the Skygrid population moves: tau, the zero mode and the HMC on the gammas
 #include "emat_state_host.hpp"      // buffers, host records, emat_backend and the transitions of its part state
@@ -635,9 +634,9 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 
 #include "emat_debug_host.hpp"      // the emat_debug_* hooks and the profiling builds' read-outs
 #include "emat_gtree_host.hpp"
-#include "emat_probe_host.hpp"
 #include "emat_mcc_host.hpp"
-#include "emat_samples_probe_host.hpp"
+#include "emat_probe_host.hpp"          // the probers' driver and the resident tree's entry points
+#include "emat_samples_probe_host.hpp"  // the store's entry points
 #include "emat_build_host.hpp"
 #include "emat_utree_host.hpp"
 #include "emat_site_rate_host.hpp"

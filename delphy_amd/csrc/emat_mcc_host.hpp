@@ -38,8 +38,6 @@ emat_status mcc_store_alloc(emat_backend* h, const std::string& w, int64_t capac
   return EMAT_OK;
 }
 
-MccMuts mcc_muts_dev(MccHost& X) { MccMuts Mu{}; Mu.hdr = X.mut_hdr.p; Mu.ref = X.mut_ref.p; Mu.arena = X.mut_arena.p; Mu.L = X.mut_L; return Mu; }
-
 // What a push on a store with mutation room checks before it writes anything: the store's number of sites, and `records` free in the arena.
 emat_status mcc_mut_room_for(emat_backend* h, const std::string& w, int64_t records) {
   const MccHost& X = h->mcc;

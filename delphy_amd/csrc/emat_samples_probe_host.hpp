@@ -1,9 +1,8 @@
-// emat_samples_probe_host.hpp -- host side of the probers over many samples of the store (emat_samples_probe_kernels.hpp), the ancestral
-// one and the site-state one, which differ in where the labels come from, in the branches and in the chain's start, and share the rest:
-// argument and state checks, the per-sample grids (emat_probe_host.hpp: probe_extend_grid, the single-tree call's arithmetic), the
-// population tables of all models in one upload (probe_pop_table), the chunks, the summaries, and the copies of what was asked for.
+// emat_samples_probe_host.hpp -- the probers over many samples of the store, the ancestral one and the site-state one: what is
+// specific to the store.  Argument and state checks, the chosen samples' root times (the one step the resident tree does not need),
+// and the job -- one unit per (sample, site) -- handed to the driver every prober shares (emat_probe_host.hpp: probe_run_job).
 //
-// Included by emat_backend.hip after emat_probe_host.hpp and emat_mcc_host.hpp (mcc_check_room, mcc_store_dev).
+// Included by emat_backend.hip after emat_probe_host.hpp (ProbeJob) and emat_mcc_host.hpp.
 #ifndef EMAT_SAMPLES_PROBE_HOST_HPP_
 #define EMAT_SAMPLES_PROBE_HOST_HPP_
 
@@ -59,152 +58,40 @@ emat_status samples_probe_run(emat_backend* h, const std::string& w, const Sampl
   const bool want_stats = out->num_ranks > 0;
   if (!out->p && !out->mean && !want_stats) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": nothing is asked for: p, mean and order_stats are all NULL");
   std::vector<HostPopModel> hps((size_t)q.num_pops);
-  size_t knots = 0;
   for (int i = 0; i < q.num_pops; ++i) {
     const std::string why = probe_host_pop(q.pops[i], hps[(size_t)i]);
     if (!why.empty()) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + ": population model " + std::to_string(i) + ": " + why);
-    knots += hps[(size_t)i].x.size();
   }
-  if (want_stats && M > k_sprobe_sort_max)
-    return fail(h, EMAT_ERR_CAPACITY, w + ": order statistics over " + std::to_string(M) + " samples, and the sort holds " + std::to_string(k_sprobe_sort_max));
-  const int32_t members = by_site ? 4 : q.num_marked + 1;
-  const int32_t U = by_site ? q.num_sites : 1;               // units of a sample
-  const size_t values = (size_t)U * (size_t)members * (size_t)q.num_t_cells;
+  if (want_stats && M > k_probe_sort_max)
+    return fail(h, EMAT_ERR_CAPACITY, w + ": order statistics over " + std::to_string(M) + " samples, and the sort holds " + std::to_string(k_probe_sort_max));
 
-  // ---- step 0: roots, grids ----
-  const MccStore D = mcc_store_dev(X);
-  const MccPick pick{q.first, q.stride, M};
-  const dim3 b256(256);
-  HIP_TRY(S.sp_root_t.alloc_roomy((size_t)M)); HIP_TRY(S.sp_status.alloc_roomy((size_t)M));
-  HIP_TRY(hipMemsetAsync(S.sp_status.p, 0, (size_t)M * 4, h->stream));
-  hipLaunchKernelGGL(k_sprobe_roots, dim3((unsigned)((M + 255) / 256)), b256, 0, h->stream, D, pick, S.sp_root_t.p, S.sp_status.p);
+  // ---- step 0: the chosen samples' root times; then the job, one unit per (sample, site) ----
+  ProbeJob J;
+  J.w = w; J.by_site = by_site; J.M = M; J.U = by_site ? q.num_sites : 1; J.members = by_site ? 4 : q.num_marked + 1;
+  J.t_start = q.t_start; J.t_end = q.t_end; J.num_t_cells = q.num_t_cells;
+  J.num_marked = q.num_marked; J.marks = q.marks; J.per_sample = q.per_sample; J.corr = q.through_corr ? X.corr.p : nullptr;
+  J.hps = std::move(hps); J.out = *out;
+  J.T.parent = X.parent.p; J.T.t = X.t.p; J.T.root = X.root.p; J.T.lists = X.mut_hdr.p; J.T.recs = X.mut_arena.p; J.T.ref = X.mut_ref.p; J.T.n = n; J.T.L = X.mut_L;
+  HIP_TRY(S.root_t.alloc_roomy((size_t)M)); HIP_TRY(S.status.alloc_roomy((size_t)M));
+  HIP_TRY(hipMemsetAsync(S.status.p, 0, (size_t)M * 4, h->stream));
+  hipLaunchKernelGGL(k_probe_roots, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, J.T, q.first, q.stride, M, S.root_t.p, S.status.p);
   HIP_TRY(hipGetLastError());
   std::vector<double> root_t((size_t)M); std::vector<int32_t> status((size_t)M);
-  HIP_TRY(hipMemcpyAsync(root_t.data(), S.sp_root_t.p, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(status.data(), S.sp_status.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(root_t.data(), S.root_t.p, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(status.data(), S.status.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  std::vector<SProbeSample> samples((size_t)M * U);        // one descriptor per unit, sample-major
-  std::vector<SProbeSeg> segs(by_site ? (size_t)M : 0);
-  int64_t stride_cells = 0;
-  for (int k = 0; k < M; ++k) {
-    const std::string which = "sample " + std::to_string(k) + " (slot " + std::to_string(q.first + k * q.stride) + ")";
-    if (status[(size_t)k]) return fail(h, EMAT_ERR_INTERNAL, w + ": the root of " + which + " is outside the tree");
-    SProbeSample& s = samples[(size_t)k * U];
-    s = SProbeSample{};
-    int64_t num_cells = 0;
-    if (!probe_extend_grid(q.t_start, q.t_end, q.num_t_cells, root_t[(size_t)k], n, members, s.grid, num_cells, s.cells_to_skip))
-      return fail(h, EMAT_ERR_CAPACITY, w + ": " + which + ": " + probe_grid_too_large(members, num_cells, root_t[(size_t)k]));
-    s.slot = q.first + k * q.stride; s.pop = q.num_pops == 1 ? 0 : k;
-    stride_cells = std::max(stride_cells, num_cells);
-    if (out->cells_to_skip) out->cells_to_skip[k] = s.cells_to_skip;
-    for (int i = 1; i < U; ++i) samples[(size_t)k * U + i] = s;
-    if (by_site) segs[(size_t)k] = SProbeSeg{(long long)X.mut_base[(size_t)s.slot], X.mut_len[(size_t)s.slot], 0};
-  }
-
-  // ---- room: what is kept for the whole call, and the chunk ----
-  const size_t nc = (size_t)stride_cells;
-  const size_t per_sample = (size_t)U * ((size_t)n * 12 + (size_t)members * nc * 16 + (size_t)members * (nc + 1) * 4 + nc * 16);
-  const size_t whole_call = (size_t)M * values * 8 + (out->mean ? values * 8 : 0) + (want_stats ? (size_t)out->num_ranks * (values * 8 + 4) : 0) +
-                            (size_t)M * ((size_t)U * sizeof(SProbeSample) + 12 + (q.per_sample ? (size_t)q.num_marked * 4 : 0) + (by_site ? sizeof(SProbeSeg) : 0)) + (size_t)q.num_pops * sizeof(PopTable) + knots * 16 +
-                            (size_t)q.num_marked * 4 + (by_site ? (size_t)U * 4 : 0);
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  const size_t avail = free_b + S.samples_bytes();          // (what the last call left is reused or replaced)
-  if (whole_call + per_sample > avail)
-    return fail(h, EMAT_ERR_CAPACITY, w + ": the results of " + std::to_string(M) + " samples x " + (by_site ? std::to_string(U) + " sites x " : std::string()) + std::to_string(members) + " members x " + std::to_string(q.num_t_cells) + " cells need " + mcc_mb(whole_call) +
-                                      " and the working room of one sample" + (by_site ? " with all its sites " : " ") + mcc_mb(per_sample) + "; the device has " + mcc_mb(free_b) + " free of " + mcc_mb(total_b));
-  int64_t B = h->cfg_samples_probe_chunk;
-  if (B <= 0) B = (int64_t)std::max<size_t>(1, (avail - whole_call) / 2 / per_sample);   // half of what is left: buffers that grow take a quarter more than asked
-  B = std::min<int64_t>(B, M);
-  if (S.samples_bytes() + free_b < whole_call + (size_t)B * per_sample) B = 1;
-  const size_t BU = (size_t)B * U;                           // units of a chunk
-  const size_t Bn = BU * (size_t)n, Bv = BU * members * nc, Bd = BU * members * (nc + 1), Bc = BU * nc;
-  if (Bn > S.sp_val.n || Bv > S.sp_fix.n || (size_t)M * values > S.sp_p.n) { HIP_TRY(hipStreamSynchronize(h->stream)); S.release_samples(); }   // (freed first, so that the room asked for is the room needed)
-  HIP_TRY(S.sp_root_t.alloc((size_t)M)); HIP_TRY(S.sp_status.alloc((size_t)M));
-  HIP_TRY(S.sp_val.alloc(Bn)); HIP_TRY(S.sp_jump_a.alloc(Bn)); HIP_TRY(S.sp_jump_b.alloc(Bn));
-  HIP_TRY(S.sp_fix.alloc(Bv)); HIP_TRY(S.sp_counts.alloc(Bv)); HIP_TRY(S.sp_diff.alloc(Bd)); HIP_TRY(S.sp_total.alloc(Bc)); HIP_TRY(S.sp_p_coalesce.alloc(Bc));
-  HIP_TRY(S.sp_p.alloc((size_t)M * values)); HIP_TRY(S.sp_samples.alloc((size_t)M * U)); HIP_TRY(S.sp_pops.alloc((size_t)q.num_pops));
-  HIP_TRY(hipMemsetAsync(S.sp_status.p, 0, (size_t)M * 4, h->stream));
-
-  // ---- uploads: descriptors, population tables with the knots of all models one after the other, marks ----
-  HIP_TRY(hipMemcpy(S.sp_samples.p, samples.data(), (size_t)M * U * sizeof(SProbeSample), hipMemcpyHostToDevice));
-  if (by_site) { HIP_TRY(S.sp_segs.upload(segs.data(), (size_t)M)); HIP_TRY(S.sp_sites.upload(q.sites, (size_t)U)); }
-  {
-    std::vector<double> xs, gs; xs.reserve(knots); gs.reserve(knots);
-    for (const HostPopModel& hp : hps) { xs.insert(xs.end(), hp.x.begin(), hp.x.end()); gs.insert(gs.end(), hp.gamma.begin(), hp.gamma.end()); }
-    if (knots) { HIP_TRY(S.sp_sky_x.upload(xs.data(), knots)); HIP_TRY(S.sp_sky_g.upload(gs.data(), knots)); }
-    std::vector<PopTable> pts; pts.reserve(hps.size());
-    size_t o = 0;
-    for (const HostPopModel& hp : hps) { pts.push_back(probe_pop_table(hp, S.sp_sky_x.p + o, S.sp_sky_g.p + o)); o += hp.x.size(); }
-    HIP_TRY(hipMemcpy(S.sp_pops.p, pts.data(), pts.size() * sizeof(PopTable), hipMemcpyHostToDevice));
-  }
-  const size_t num_marks = by_site ? 0 : (size_t)q.num_marked * (q.per_sample ? (size_t)M : 1);
-  if (num_marks) HIP_TRY(S.sp_marks.upload(q.marks, num_marks));
-
-  // ---- steps 1 to 3, chunk by chunk ----
-  const int32_t* corr = q.through_corr ? X.corr.p : nullptr;
-  const MccMuts Mu = mcc_muts_dev(X);
-  for (int64_t k0 = 0; k0 < M; k0 += B) {
-    const int32_t Bk = (int32_t)std::min<int64_t>(B, M - k0) * U;   // the chunk's units: what the kernels index
-    SProbeChunk C{}; C.samples = S.sp_samples.p; C.k0 = (int32_t)k0 * U; C.B = Bk; C.n = n; C.num_members = members; C.stride_cells = (int32_t)stride_cells;
-    const unsigned gy = (unsigned)std::min(Bk, 65535);
-    const dim3 per_node((unsigned)((n + 255) / 256), gy);
-    if (!by_site) HIP_TRY(hipMemsetAsync(S.sp_val.p, 0xff, (size_t)Bk * n * 4, h->stream));
-    HIP_TRY(hipMemsetAsync(S.sp_fix.p, 0, (size_t)Bk * members * nc * 8, h->stream));
-    HIP_TRY(hipMemsetAsync(S.sp_diff.p, 0, (size_t)Bk * members * (nc + 1) * 4, h->stream));
-    if (by_site) {
-      hipLaunchKernelGGL(k_sprobe_site_flags, per_node, b256, 0, h->stream, D, Mu, C, (const SProbeSeg*)S.sp_segs.p, (const int32_t*)S.sp_sites.p, (int)U, S.sp_val.p, S.sp_status.p);
-      HIP_TRY(hipGetLastError());
-    } else if (q.num_marked > 0) {
-      hipLaunchKernelGGL(k_sprobe_marks, dim3((unsigned)((q.num_marked + 255) / 256), gy), b256, 0, h->stream, C, (const int32_t*)S.sp_marks.p, (int)q.num_marked, q.per_sample ? (int)q.num_marked : 0, corr, S.sp_val.p);
-      HIP_TRY(hipGetLastError());
+  J.units.resize((size_t)M * J.U);
+  for (int k = 0; k < M; ++k)
+    for (int i = 0; i < J.U; ++i) {
+      ProbeUnit& u = J.units[(size_t)k * J.U + i];
+      u = ProbeUnit{};
+      u.slot = q.first + k * q.stride; u.pop = q.num_pops == 1 ? 0 : k; u.sample = k; u.ref_state = -1;   // (the root starts from the sequence the slot kept)
+      if (by_site) { u.site = q.sites[i]; u.seg_base = (long long)X.mut_base[(size_t)u.slot]; u.seg_len = X.mut_len[(size_t)u.slot]; }
     }
-    hipLaunchKernelGGL(k_sprobe_jump_init, per_node, b256, 0, h->stream, D, C, members - 1, S.sp_val.p, S.sp_jump_a.p);
-    HIP_TRY(hipGetLastError());
-    int32_t* cur = S.sp_jump_a.p; int32_t* nxt = S.sp_jump_b.p;
-    for (int64_t reach = 1; reach < n; reach *= 2) {   // ceil(log2 n) rounds cover any depth
-      hipLaunchKernelGGL(k_sprobe_jump_double, per_node, b256, 0, h->stream, n, Bk, (const int32_t*)cur, nxt);
-      HIP_TRY(hipGetLastError());
-      std::swap(cur, nxt);
-    }
-    if (by_site) hipLaunchKernelGGL(k_sprobe_site_branches, per_node, b256, 0, h->stream, D, C, (int)U, (const int32_t*)S.sp_val.p, (const int32_t*)cur, S.sp_fix.p, S.sp_diff.p, S.sp_status.p);
-    else hipLaunchKernelGGL(k_sprobe_branches, per_node, b256, 0, h->stream, D, C, (const int32_t*)S.sp_val.p, (const int32_t*)cur, S.sp_fix.p, S.sp_diff.p, S.sp_status.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sprobe_counts, dim3((unsigned)members, gy), dim3(k_wave), 0, h->stream, C, (const unsigned long long*)S.sp_fix.p, (const int32_t*)S.sp_diff.p, S.sp_counts.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sprobe_cells, dim3((unsigned)((stride_cells + 63) / 64), gy), dim3(64), 0, h->stream, C, (const PopTable*)S.sp_pops.p, (const double*)S.sp_counts.p, S.sp_total.p, S.sp_p_coalesce.p);
-    HIP_TRY(hipGetLastError());
-    if (by_site) hipLaunchKernelGGL(k_sprobe_site_chain, dim3((unsigned)((members + 63) / 64), gy), dim3(64), 0, h->stream, D, C, (int)q.num_t_cells, (const int32_t*)S.sp_val.p, (const double*)S.sp_counts.p, (const double*)S.sp_total.p, (const double*)S.sp_p_coalesce.p, S.sp_p.p);
-    else hipLaunchKernelGGL(k_sprobe_chain, dim3((unsigned)((members + 63) / 64), gy), dim3(64), 0, h->stream, C, (int)q.num_t_cells, (const double*)S.sp_counts.p, (const double*)S.sp_total.p, (const double*)S.sp_p_coalesce.p, S.sp_p.p);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipMemcpyAsync(status.data(), S.sp_status.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  for (int k = 0; k < M; ++k) {
-    const std::string which = "sample " + std::to_string(k) + " (slot " + std::to_string(q.first + k * q.stride) + ")";
-    if (status[(size_t)k] & k_sprobe_bad_link) return fail(h, EMAT_ERR_INTERNAL, w + ": a link of " + which + " leaves the tree");
-    if (status[(size_t)k] & k_sprobe_bad_list) return fail(h, EMAT_ERR_INTERNAL, w + ": a mutation list of " + which + " lies outside the sample's segment of the arena");
-    if (status[(size_t)k] & k_sprobe_negative_branch) return fail(h, EMAT_ERR_INTERNAL, w + ": a node of " + which + " is earlier than its parent (the reference's add_boxcar refuses left > right)");
-  }
-
-  // ---- step 4: summaries, and the copies ----
-  if (out->mean) {
-    HIP_TRY(S.sp_mean.alloc(values));
-    hipLaunchKernelGGL(k_sprobe_mean, dim3((unsigned)((values + 255) / 256)), b256, 0, h->stream, (const double*)S.sp_p.p, (int)M, values, S.sp_mean.p);
-    HIP_TRY(hipGetLastError());
-  }
-  if (want_stats) {
-    HIP_TRY(S.sp_stats.alloc((size_t)out->num_ranks * values)); HIP_TRY(S.sp_ranks.upload(out->ranks, (size_t)out->num_ranks));
-    int padded = 1; while (padded < M) padded *= 2;
-    hipLaunchKernelGGL(k_sprobe_order_stats, dim3((unsigned)std::min<size_t>(values, 1 << 16)), dim3(k_sprobe_sort_threads), (size_t)padded * sizeof(double), h->stream,
-                       (const double*)S.sp_p.p, (int)M, padded, values, (const int32_t*)S.sp_ranks.p, (int)out->num_ranks, S.sp_stats.p);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (out->p) HIP_TRY(hipMemcpy(out->p, S.sp_p.p, (size_t)M * values * 8, hipMemcpyDeviceToHost));
-  if (out->mean) HIP_TRY(hipMemcpy(out->mean, S.sp_mean.p, values * 8, hipMemcpyDeviceToHost));
-  if (want_stats) HIP_TRY(hipMemcpy(out->order_stats, S.sp_stats.p, (size_t)out->num_ranks * values * 8, hipMemcpyDeviceToHost));
-  return EMAT_OK;
+  for (int k = 0; k < M; ++k)
+    if (status[(size_t)k]) return fail(h, EMAT_ERR_INTERNAL, w + ": the root of " + J.which(k) + " is outside the tree");
+  st = probe_plan_grids(h, J, root_t.data()); if (st) return st;
+  return probe_run_job(h, J);
 }
 
 }  // namespace

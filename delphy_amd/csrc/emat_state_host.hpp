@@ -136,27 +136,18 @@ struct SkygridScratch {
   int32_t first_cell = 0, num_cells = 0, num_inner = 0;
 };
 
-// Scratch of the tree probers (emat_probe_kernels.hpp, emat_probe_host.hpp): allocated at the first call, grown on demand.
+// Scratch of the tree probers (emat_probe_kernels.hpp, emat_probe_host.hpp), one set for the resident tree and for the samples of the store:
+// the working room of a chunk of units, the per-unit results the summaries are made from, and `args`, everything a call brings from the
+// host in one upload.  Allocated at the first call, grown on demand; released with the store, which sized the largest of it, and back
+// at the next call.
 struct ProbeScratch {
-  DevBuf<int32_t> val, jump_a, jump_b, marked, diff, status;
+  DevBuf<int32_t> val, jump_a, jump_b, diff, status;
   DevBuf<unsigned long long> fix;
-  DevBuf<double> counts, total, p_coalesce, p, sky_x, sky_g;
-  // emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors (emat_samples_probe_kernels.hpp, emat_samples_probe_host.hpp): the working room of
-  // a chunk of samples, the descriptors and population tables of all chosen samples, and the per-sample results the summaries are made from
-  DevBuf<int32_t> sp_val, sp_jump_a, sp_jump_b, sp_marks, sp_diff, sp_status, sp_ranks;
-  DevBuf<unsigned long long> sp_fix;
-  DevBuf<double> sp_counts, sp_total, sp_p_coalesce, sp_p, sp_mean, sp_stats, sp_root_t, sp_sky_x, sp_sky_g;
-  DevBuf<SProbeSample> sp_samples; DevBuf<PopTable> sp_pops;
-  DevBuf<SProbeSeg> sp_segs; DevBuf<int32_t> sp_sites;   // the site-state form: the chosen samples' segments of the mutation arena, the sites asked for
+  DevBuf<double> counts, total, p_coalesce, p, mean, stats, root_t;
+  DevBuf<uint8_t> args;   // descriptors, population tables and their knots, marks, ranks
   template <class T> static void drop(DevBuf<T>& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 0; }
-  size_t samples_bytes() const {
-    return (sp_val.n + sp_jump_a.n + sp_jump_b.n + sp_marks.n + sp_diff.n + sp_status.n + sp_ranks.n) * 4 + (sp_fix.n + sp_counts.n + sp_total.n + sp_p_coalesce.n + sp_p.n + sp_mean.n + sp_stats.n + sp_root_t.n + sp_sky_x.n + sp_sky_g.n) * 8 +
-           sp_samples.n * sizeof(SProbeSample) + sp_pops.n * sizeof(PopTable) + sp_segs.n * sizeof(SProbeSeg) + sp_sites.n * 4;
-  }
-  void release_samples() {   // with the store (MccHost::release): what was sized by it goes with it
-    drop(sp_val); drop(sp_jump_a); drop(sp_jump_b); drop(sp_marks); drop(sp_diff); drop(sp_status); drop(sp_ranks); drop(sp_fix); drop(sp_counts); drop(sp_total); drop(sp_p_coalesce);
-    drop(sp_p); drop(sp_mean); drop(sp_stats); drop(sp_root_t); drop(sp_sky_x); drop(sp_sky_g); drop(sp_samples); drop(sp_pops); drop(sp_segs); drop(sp_sites);
-  }
+  size_t samples_bytes() const { return (val.n + jump_a.n + jump_b.n + diff.n + status.n) * 4 + (fix.n + counts.n + total.n + p_coalesce.n + p.n + mean.n + stats.n + root_t.n) * 8 + args.n; }
+  void release_samples() { drop(val); drop(jump_a); drop(jump_b); drop(diff); drop(status); drop(fix); drop(counts); drop(total); drop(p_coalesce); drop(p); drop(mean); drop(stats); drop(root_t); drop(args); }
 };
 
 // The store of sampled trees and what emat_mcc_derive works in (emat_mcc_kernels.hpp, emat_mcc_host.hpp).  The store is sized by
