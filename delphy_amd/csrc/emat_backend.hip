@@ -164,7 +164,7 @@ emat_status emat_begin_upload(emat_backend* h, int32_t num_parts) {
   h->fatal_status = EMAT_OK; h->fatal_message.clear(); h->pass_pending = false;
   h->parts.clear(); h->parts.resize(num_parts);
   h->expected_moves.assign((size_t)num_parts, 0);
-  h->uploads_expected = num_parts; h->root_part = -1; h->gt.parts_live = false;
+  h->uploads_expected = num_parts; h->root_part = -1; h->gt.parts_came_back();   // (host parts replace whatever the resident tree had out)
   h->parts_replaced();
   return EMAT_OK;
 }

@@ -59,9 +59,7 @@ int64_t mcc_mut_take(MccHost& X, int32_t slot, int64_t records) {
 
 // What every call on the store starts with; `need_tree`: the resident tree is read (and so must not be out on its slabs).
 emat_status mcc_require(emat_backend* h, const std::string& w, bool need_tree) {
-  emat_status st = gt_require(h, need_tree); if (st) return st;
-  if (need_tree && h->gt.parts_live) return fail(h, EMAT_ERR_STATE, w + ": the parts are out on their slabs: emat_tree_reassemble first");
-  return EMAT_OK;
+  return need_tree ? gt_require_tree_home(h, false, w + ": ") : gt_require(h, false);
 }
 emat_status mcc_require_store(emat_backend* h, const std::string& w) {
   const MccHost& X = h->mcc;

@@ -132,6 +132,15 @@ emat_status upload_shared_cells(emat_backend* h) {
   return EMAT_OK;
 }
 
+// The per-part device words of a pass, sized for `parts` parts and zeroed on the engine's stream: the status of every part, and its ticks
+// (entry / exit of the part, + entry / exit of the first k_ticket_log tickets of every part).
+emat_status reset_part_words(emat_backend* h, size_t parts) {
+  const size_t ticks = (2 + 2 * k_ticket_log) * parts;
+  HIP_TRY(h->d_part_ticks.alloc(ticks)); HIP_TRY(hipMemsetAsync(h->d_part_ticks.p, 0, ticks * sizeof(int64_t), h->stream));
+  HIP_TRY(h->d_part_status.alloc(parts)); HIP_TRY(hipMemsetAsync(h->d_part_status.p, 0, parts * sizeof(int32_t), h->stream));
+  return EMAT_OK;
+}
+
 // Encode all parts and push them to the device.
 emat_status materialize(emat_backend* h) {
   if (!bind_device(h)) return fail(h, EMAT_ERR_HIP, "hipSetDevice failed");
@@ -176,8 +185,8 @@ emat_status materialize(emat_backend* h) {
   { emat_status st = upload_shared_cells(h); if (st) return st; }
   HIP_TRY(h->d_slabs.upload(h->h_slabs.data(), h->h_slabs.size()));
   HIP_TRY(h->d_slab_off.upload(offs.data(), offs.size()));
-  { std::vector<int64_t> z((2 + 2 * k_ticket_log) * h->parts.size(), 0); HIP_TRY(h->d_part_ticks.upload(z.data(), z.size())); }   // + entry / exit ticks of the first k_ticket_log tickets of every part
-  { std::vector<int32_t> z(h->parts.size(), 0); HIP_TRY(h->d_part_status.upload(z.data(), z.size())); }
+  { emat_status st = reset_part_words(h, h->parts.size()); if (st) return st; }
+  HIP_TRY(hipStreamSynchronize(h->stream));   // (everything else here is a blocking copy: the zeros have landed too when this returns, whichever stream runs the parts next)
   h->slabs_on_device = true; h->host_slabs_current = true; h->derived_valid = all_kept;
   return EMAT_OK;
 }

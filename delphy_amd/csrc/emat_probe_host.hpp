@@ -281,9 +281,8 @@ emat_status probe_run_job(emat_backend* h, ProbeJob& J) {
 emat_status probe_resident_job(emat_backend* h, const char* what, const ProbeRequest& q, ProbeJob& J) {
   J.w = what;
   const std::string& w = J.w;
-  emat_status st = gt_require(h, true); if (st) return st;
+  emat_status st = gt_require_tree_home(h, false, w + ": "); if (st) return st;
   GTreeHost& G = h->gt;
-  if (G.parts_live) return fail(h, EMAT_ERR_STATE, w + ": the parts are out on their slabs: emat_tree_reassemble first");
   const int n = G.n;
   ProbeUnit u{};
   if (q.kind == EMAT_PROBE_ANCESTORS) {

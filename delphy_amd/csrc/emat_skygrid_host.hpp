@@ -76,9 +76,8 @@ emat_status sky_run(emat_backend* h, const HostPopModel& hp, const emat_skygrid_
 
 // Scalable_coalescent_prior's grid and the inner nodes' times of the tree in HBM, into h->sky (k_bar, inner_t, first_cell, num_cells, num_inner).
 emat_status sky_tree_stats(emat_backend* h, const std::string& w, double t_ref, double t_step) {
-  emat_status st = gt_require(h, true); if (st) return st;
+  emat_status st = gt_require_tree_home(h, false, w); if (st) return st;
   GTreeHost& G = h->gt;
-  if (G.parts_live) return fail(h, EMAT_ERR_STATE, w + "the parts are out on their slabs: emat_tree_reassemble first");
   if (h->pass_pending) { st = finish_pass(h); if (st) return st; }
   SkygridScratch& S = h->sky;
   const GTreeDev T = G.dev();

@@ -122,14 +122,19 @@ SlabGeo slab_geometry(const emat_backend* h, int n, int num_muts, uint32_t conte
   g.bytes = (uint32_t)sizeof(SlabHeader) + (uint32_t)n * (uint32_t)sizeof(NodeRec) + miss_dl_bytes_for((uint32_t)n) + a16((uint32_t)g.cell_cap * cell_bytes_for(includes_run_root)) + a16((uint32_t)trace_cap * 32u) + g.heap + g.scratch;
   return g;
 }
-void place_slab(emat_backend* h, size_t p, const SlabGeo& g, uint64_t& off, uint32_t content_bytes) {
+// What the handle books per part about a slab of geometry g (the size classes and the staging variants read these) ...
+void book_slab_bytes(emat_backend* h, size_t p, const SlabGeo& g, uint32_t content_bytes) {
   if (h->used_bytes.size() <= p) h->used_bytes.resize(p + 1, 0u);
   h->used_bytes[p] = g.bytes - g.scratch - g.heap + content_bytes;
-  PartHost& ph = h->parts[p];
-  ph.slab_off = off; ph.slab_bytes = g.bytes; ph.scratch_bytes = g.scratch; off += g.bytes;
   h->persistent_bytes[p] = g.bytes - g.scratch;
   h->prefix_bytes[p] = g.bytes - g.scratch - g.heap;
   h->max_slab_bytes = std::max(h->max_slab_bytes, g.bytes);
+}
+// ... and where the slab goes, into the part's record (a repartition on the device writes its records later, in its one pass over them)
+void place_slab(emat_backend* h, size_t p, const SlabGeo& g, uint64_t& off, uint32_t content_bytes) {
+  book_slab_bytes(h, p, g, content_bytes);
+  PartHost& ph = h->parts[p];
+  ph.slab_off = off; ph.slab_bytes = g.bytes; ph.scratch_bytes = g.scratch; off += g.bytes;
 }
 // Size classes: which parts share a launch and an LDS staging area.  Class 0 has the largest area; the last class (the
 // "main" one) holds the bulk of the parts.  Sets h->class_of / class_lds / class_begin; build_order lays the launch

@@ -116,6 +116,35 @@ struct GTreeHost {
   // Whoever touches the device-resident tree next (gt_require) waits for it and checks how it went (gt_finish_gather).
   bool gather_pending = false; std::vector<GRootDelta> gather_rd;
   emat_status gather_failed = EMAT_OK; std::string gather_failed_text;   // a deferred gather that failed: sticky until emat_tree_upload (gt_require)
+  // The flags above (resident, parts_live, P, partition_on_device, measure_queued, d_kids_current, full_mirrors_stale, climb_current,
+  // gather_pending, gather_failed) are written only by the transitions below.
+  void tree_uploaded() {            // a new tree: no partition (one made of the tree that was here says nothing about this one), no parts, mirrors as uploaded
+    resident = true; parts_live = false; P = 0; partition_on_device = false; measure_queued = false;
+    full_mirrors_stale = false; d_kids_current = false; climb_current = false;
+    gather_pending = false; gather_failed = EMAT_OK; gather_failed_text.clear();
+  }
+  void partition_made(int32_t parts, int32_t root) { P = parts; root_part = root; partition_on_device = true; measure_queued = false; h_orig.clear(); h_kid0.clear(); }   // by emat_tree_partition, on the device
+  void measure_was_queued() { measure_queued = true; }                       // ... with k_gt_measure behind it
+  void partition_dropped() { P = 0; partition_on_device = false; measure_queued = false; }   // ... which the device then refused
+  bool take_queued_measure() { const bool q = measure_queued; measure_queued = false; return q; }   // a repartition uses the queued measures, or makes its own
+  void parts_recalled(int32_t parts, int32_t root) { P = parts; root_part = root; parts_live = false; }   // a repartition begins: whatever was out on slabs is about to be rebuilt
+  void partition_handed_in() { partition_on_device = false; }                // as arrays: the host copies are the caller's
+  void parts_went_out() { parts_live = true; }                               // k_gt_build wrote the slabs
+  void parts_came_back() { parts_live = false; }                             // gathered (or about to be: a deferred gather), or replaced by host parts (emat_begin_upload)
+  void kids_packed() { d_kids_current = true; }                              // k_gt_pack_kids filled d_kids
+  void links_fetched() { d_kids_current = true; full_mirrors_stale = true; } // new links in d_kids / pin_kids, root and root time on the host; the separate arrays lag
+  void mirrors_refreshed() { full_mirrors_stale = false; }
+  void lists_or_links_rewritten() { climb_current = false; }                 // (a gather, an apply)
+  void climb_remade() { climb_current = true; }
+  void gather_deferred() { gather_pending = true; }                          // launched, not yet waited for
+  void gather_finished() { gather_pending = false; }
+  void gather_went_wrong(emat_status st, const std::string& text) { gather_failed = st; gather_failed_text = text; }   // stays pending and failed until tree_uploaded
+  // The three list heaps in one place: f(heap, k) with used[k] the records in use; the record type is the heap's element type.
+  template <class F> emat_status for_each_heap(F&& f) {
+    if (emat_status st = f(mut_heap, 0)) return st;
+    if (emat_status st = f(iv_heap, 1)) return st;
+    return f(fs_heap, 2);
+  }
   const int32_t* kids() const { return (const int32_t*)pin_kids.data(); }   // [2 v] = child0, [2 v + 1] = child1
   GTreeDev dev() {
     GTreeDev g{};

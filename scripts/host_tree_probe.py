@@ -1,6 +1,7 @@
 """Whole cycles with the tree on the HOST (the adaptor of INTEGRATION sections 2-3: Run keeps its Phylo_tree), by phase.
-  EMAT_VERBOSE=1 python scripts/host_tree_probe.py [cycles=6] [max_part_nodes=-1]     (reports per call on stderr)
-  EMAT_VERBOSE=spans ...                                                             (host spans summed at exit)"""
+  EMAT_VERBOSE=1 python scripts/host_tree_probe.py [cycles=6] [max_part_nodes=-1] [threads=0] [resident]     (reports per call on stderr)
+  EMAT_VERBOSE=spans ...                                                             (host spans summed at exit)
+`resident`: the same cycles with the tree in HBM (emat_tree_*: the spans tree_partition / tree_repartition / tree_reassemble)."""
 import sys, os, time
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import delphy_amd as d
@@ -14,6 +15,8 @@ sc = make_scenario("C4")
 b = d.EmatBackend(sc.num_sites)
 run = d.EmatRun(b, sc.tree, sc.ref, 20261001)
 run.set_num_parts(8192); run.set_max_part_nodes(limit); run.set_hky(sc.mu, sc.kappa, sc.pi); run.set_pop_model(sc.pop)
+if len(sys.argv) > 4 and sys.argv[4] == "resident":
+    run.set_device_tree(True)
 per = 50 * sc.tree.num_nodes
 run.do_mcmc_steps(per, per)
 t0 = time.perf_counter()
