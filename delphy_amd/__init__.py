@@ -10,6 +10,8 @@ from .engine import (  # noqa: F401
     EmatError,
     EmatMultiRun,
     EmatRun,
+    ExpPopMovesResult,
+    ExpPopSpec,
     FlatTree,
     MccTree,
     PopModel,

@@ -35,6 +35,7 @@
 #include "emat_mcc_kernels.hpp"     // sampled trees kept in HBM, and the maximum-clade-credibility tree derived from them
 #include "emat_site_rate_kernels.hpp"   // the site-rate moves: steps on alpha and the Gibbs draw of every nu_l
 #include "emat_skygrid_kernels.hpp"     // the Skygrid population moves: tau, the zero mode and the HMC on the gammas
+#include "emat_exp_pop_kernels.hpp"     // the Exponential population moves: n0 and the growth rate
 #include "emat_state_host.hpp"      // buffers, host records, emat_backend and the transitions of its part state
 #include "emat_slab_host.hpp"       // slab codec, geometry, size classes
 #include "emat_pass_host.hpp"       // materialize, launch_moves, finish_pass, the two pulls
@@ -641,3 +642,4 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 #include "emat_utree_host.hpp"
 #include "emat_site_rate_host.hpp"
 #include "emat_skygrid_host.hpp"
+#include "emat_exp_pop_host.hpp"

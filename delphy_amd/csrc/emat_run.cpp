@@ -51,6 +51,7 @@ struct RunDriver {
   bool site_rate_moves_on = false; double site_rate_alpha = 1.0; uint64_t site_rate_rounds = 0;   // Run::alpha_ and how many rounds of site-rate moves have drawn a key
   bool have_pop = false; emat_pop_model pop{}; std::vector<double> sky_x, sky_g;
   bool skygrid_moves_on = false; emat_skygrid_spec sky_spec{}; uint64_t skygrid_rounds = 0;   // Run's Skygrid settings with skygrid_tau_, and how many rounds of the Skygrid moves have drawn a key
+  bool exp_pop_moves_on = false; emat_exp_pop_spec xp_spec{}; uint64_t exp_pop_rounds = 0;      // Run's Exp_pop_model settings, and how many rounds of the Exponential moves have drawn a key
   double t_step = 1.0; bool t_step_set = false;
   int only_displacing_inner_nodes = 0, topology_moves_enabled = 1;
   bool reference_remainder = false;   // the remainder of count / parts goes to part 0 as in Run::run_local_moves (run.cpp:683-689), instead of one move per part
@@ -496,7 +497,34 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // One cycle after another (run.cpp:622-657; of the global moves, the site-rate and the Skygrid groups when they are on)
+  // Run::pop_size_move + pop_growth_rate_move, xp_spec.rounds times (run.cpp:754-764), on the device, on the ASSEMBLED tree as the Skygrid moves.
+  static constexpr uint64_t kExpPopKeyTag = 0x455850504F503031ull;   // "EXPPOP01"
+  emat_status exp_pop_moves(emat_exp_pop_result* out) {
+    EMAT_TRY(need_backend());
+    if (tree_cut) return fail(EMAT_ERR_STATE, "the Exponential population moves need the tree assembled: reassemble first");
+    if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
+    EMAT_TRY(need_pop_model());
+    if (pop.kind != EMAT_POP_EXP) return fail(EMAT_ERR_INVALID_ARGUMENT, "the Exponential population moves need an exponential population model");
+    uint32_t w[4]; philox4x32_10_pure(exp_pop_rounds, seed ^ kExpPopKeyTag, w);
+    const uint64_t key = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    emat_exp_pop_result res{};
+    if (out) { res.trace = out->trace; res.trace_capacity = out->trace_capacity; }
+    const emat_pop_model pm = pop_view();
+    const double t_ref = tree.t_max_tip(), ts = coalescent_step();
+    if (device_tree && device_tree_uploaded) EMAT_TRY(bk(emat_tree_exp_pop_moves(backend, &pm, &xp_spec, t_ref, ts, key, &res)));
+    else {
+      int32_t first_cell = 0; std::vector<double> k_bar, inner_t;
+      host_tree_coalescent_stats(t_ref, ts, first_cell, k_bar, inner_t);
+      EMAT_TRY(bk(emat_exp_pop_moves(backend, &pm, &xp_spec, t_ref, ts, first_cell, (int32_t)k_bar.size(), k_bar.data(), (int32_t)inner_t.size(), inner_t.data(), key, &res)));
+    }
+    ++exp_pop_rounds;
+    pop.p[1] = res.n0; pop.p[2] = res.g;
+    pop_model_changed();
+    if (out) *out = res;
+    return EMAT_OK;
+  }
+
+  // One cycle after another (run.cpp:622-657; of the global moves, the site-rate, the Skygrid and the Exponential groups when they are on)
   emat_status do_mcmc_steps(int64_t steps, int64_t per_cycle) {
     EMAT_TRY(need_backend());
     if (shard_world > 1) return fail(EMAT_ERR_STATE, "a sharded run is cycled by its caller, who owns the collectives (see emat_host.h)");
@@ -504,6 +532,7 @@ struct RunDriver {
     for (int64_t done = 0; done < steps;) {
       HostLaps laps(verbose_reports());
       if (skygrid_moves_on) EMAT_TRY(skygrid_moves(nullptr));   // on the whole tree, BEFORE the repartition, which then builds the parts' tables from the new curve (emat_host.h)
+      if (exp_pop_moves_on) EMAT_TRY(exp_pop_moves(nullptr));   // likewise
       EMAT_TRY(repartition());
       laps.lap(); laps.mark("cycle: 1 repartition");
       if (site_rate_moves_on) EMAT_TRY(site_rate_moves(nullptr));   // where the reference runs its global moves (run.cpp:635-641)
@@ -804,6 +833,26 @@ emat_status emat_run_get_skygrid(emat_run* r, double* gamma, double* tau) {
   if (!r->d.have_pop || r->d.pop.kind != EMAT_POP_SKYGRID) return r->d.fail(EMAT_ERR_STATE, "emat_run_get_skygrid: the run has no Skygrid population model");
   if (gamma) std::copy(r->d.sky_g.begin(), r->d.sky_g.end(), gamma);
   if (tau) *tau = r->d.sky_spec.tau;
+  return EMAT_OK;
+}
+emat_status emat_run_set_exp_pop_moves(emat_run* r, int32_t on, const emat_exp_pop_spec* spec) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!spec) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: spec must not be null");
+  const emat_exp_pop_spec& s = *spec;
+  if (!(s.g_min <= s.g_max)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: g_min must not exceed g_max, and neither may be NaN");
+  if (!std::isfinite(s.g_prior_scale) || !(s.g_prior_scale > 0.0)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: g_prior_scale must be finite and positive");
+  if (!std::isfinite(s.g_prior_mu) || !std::isfinite(s.inv_n0_prior_alpha) || !std::isfinite(s.inv_n0_prior_beta))
+    return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: g_prior_mu, inv_n0_prior_alpha and inv_n0_prior_beta must be finite");
+  if (s.rounds < 0) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: rounds must not be negative");
+  r->d.exp_pop_moves_on = on != 0; r->d.xp_spec = s;
+  return EMAT_OK;
+}
+emat_status emat_run_exp_pop_moves(emat_run* r, emat_exp_pop_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.exp_pop_moves(out); }
+emat_status emat_run_get_exp_pop(emat_run* r, double* n0, double* g) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!r->d.have_pop || r->d.pop.kind != EMAT_POP_EXP) return r->d.fail(EMAT_ERR_STATE, "emat_run_get_exp_pop: the run has no exponential population model");
+  if (n0) *n0 = r->d.pop.p[1];
+  if (g) *g = r->d.pop.p[2];
   return EMAT_OK;
 }
 emat_status emat_run_get_site_rates(emat_run* r, double* alpha, double* nu_l) {

@@ -165,6 +165,12 @@ struct SkygridScratch {
   int32_t first_cell = 0, num_cells = 0, num_inner = 0;
 };
 
+// What the Exponential population moves work in beyond the statistics in SkygridScratch (emat_exp_pop_kernels.hpp, emat_exp_pop_host.hpp): grow-only.
+struct ExpPopScratch {
+  DevBuf<double> state, partials, result;
+  DevBuf<emat_exp_pop_step> trace;
+};
+
 // Scratch of the tree probers (emat_probe_kernels.hpp, emat_probe_host.hpp), one set for the resident tree and for the samples of the store:
 // the working room of a chunk of units, the per-unit results the summaries are made from, and `args`, everything a call brings from the
 // host in one upload.  Allocated at the first call, grown on demand; released with the store, which sized the largest of it, and back
@@ -296,6 +302,7 @@ struct emat_backend {
   GTreeHost gt;                     // the whole tree, when it lives in HBM (emat_tree_upload)
   ProbeScratch probe;               // what emat_tree_probe_* / emat_tree_branch_counts work in
   SkygridScratch sky;               // what emat_skygrid_moves / emat_tree_coalescent_stats work in
+  ExpPopScratch xp;                 // what emat_exp_pop_moves works in
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
   int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs

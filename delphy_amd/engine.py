@@ -203,6 +203,72 @@ def _skygrid_result_c(num_knots: int, hmc_steps: int, trace: bool):
     return res, gamma, tr
 
 
+class _ExpPopSpecC(C.Structure):
+    _fields_ = [("n0_move_enabled", C.c_int32), ("g_move_enabled", C.c_int32), ("inv_n0_prior_alpha", C.c_double), ("inv_n0_prior_beta", C.c_double),
+                ("g_prior_mu", C.c_double), ("g_prior_scale", C.c_double), ("g_min", C.c_double), ("g_max", C.c_double), ("rounds", C.c_int32), ("pad_", C.c_int32)]
+
+
+class _ExpPopStepC(C.Structure):
+    _fields_ = [("proposed", C.c_double), ("log_coalescent_prior_proposed", C.c_double), ("log_prior_ratio", C.c_double), ("log_metropolis", C.c_double), ("u", C.c_double),
+                ("accepted", C.c_int32), ("evaluated", C.c_int32)]
+
+
+class _ExpPopResultC(C.Structure):
+    _fields_ = [("n0", C.c_double), ("g", C.c_double), ("log_coalescent_prior_start", C.c_double), ("log_coalescent_prior_end", C.c_double), ("delta_log_other_priors", C.c_double),
+                ("n0_accepted", C.c_int32), ("g_accepted", C.c_int32), ("g_out_of_bounds", C.c_int32), ("pad_", C.c_int32),
+                ("trace", C.POINTER(_ExpPopStepC)), ("trace_capacity", C.c_int32)]
+
+
+EXP_POP_STEP_DTYPE = np.dtype([("proposed", "f8"), ("log_coalescent_prior_proposed", "f8"), ("log_prior_ratio", "f8"), ("log_metropolis", "f8"), ("u", "f8"),
+                               ("accepted", "i4"), ("evaluated", "i4")])
+
+
+@dataclass
+class ExpPopSpec:
+    """The settings of the Exponential population moves (include/emat_backend.h: emat_exp_pop_spec); the defaults are the reference's."""
+    n0_move_enabled: bool = True
+    g_move_enabled: bool = True
+    inv_n0_prior_alpha: float = 0.0
+    inv_n0_prior_beta: float = 0.0
+    g_prior_mu: float = 0.001 / 365.0
+    g_prior_scale: float = 30.701135 / 365.0
+    g_min: float = -math.inf
+    g_max: float = math.inf
+    rounds: int = 50
+
+    def c_struct(self) -> "_ExpPopSpecC":
+        return _ExpPopSpecC(int(self.n0_move_enabled), int(self.g_move_enabled), float(self.inv_n0_prior_alpha), float(self.inv_n0_prior_beta),
+                            float(self.g_prior_mu), float(self.g_prior_scale), float(self.g_min), float(self.g_max), int(self.rounds), 0)
+
+
+@dataclass
+class ExpPopMovesResult:
+    """What emat_exp_pop_moves returns (include/emat_backend.h: emat_exp_pop_result)."""
+    n0: float
+    g: float
+    log_coalescent_prior_start: float
+    log_coalescent_prior_end: float
+    delta_log_other_priors: float
+    n0_accepted: int
+    g_accepted: int
+    g_out_of_bounds: int
+    trace: Optional[np.ndarray]    # [2 * rounds] records of EXP_POP_STEP_DTYPE (even: n0 steps, odd: g steps), or None when not asked for
+
+    @staticmethod
+    def _of(res: "_ExpPopResultC", trace):
+        return ExpPopMovesResult(res.n0, res.g, res.log_coalescent_prior_start, res.log_coalescent_prior_end, res.delta_log_other_priors,
+                                 res.n0_accepted, res.g_accepted, res.g_out_of_bounds, trace)
+
+
+def _exp_pop_result_c(rounds: int, trace: bool):
+    res = _ExpPopResultC()
+    steps = 2 * max(0, int(rounds))
+    tr = np.zeros(max(1, steps), EXP_POP_STEP_DTYPE) if trace else None
+    if trace:
+        res.trace = tr.ctypes.data_as(C.POINTER(_ExpPopStepC)); res.trace_capacity = steps
+    return res, (None if tr is None else tr[:steps])
+
+
 @dataclass
 class SamplesProbe:
     """What emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors return (include/emat_backend.h: emat_samples_probe_result).
@@ -487,6 +553,9 @@ def load_library():
         "emat_debug_pop_gradient": [B, P(_PopModelC), i32, i32, i32, P(dbl), P(dbl), P(dbl)],
         "emat_tree_coalescent_stats": [B, dbl, dbl, P(i32), P(i32), P(dbl), i32, P(dbl), i32, P(i32)],
         "emat_tree_skygrid_moves": [B, P(_PopModelC), P(_SkygridSpecC), dbl, dbl, u64, P(_SkygridResultC)],
+        "emat_exp_pop_moves": [B, P(_PopModelC), P(_ExpPopSpecC), dbl, dbl, i32, i32, P(dbl), i32, P(dbl), u64, P(_ExpPopResultC)],
+        "emat_tree_exp_pop_moves": [B, P(_PopModelC), P(_ExpPopSpecC), dbl, dbl, u64, P(_ExpPopResultC)],
+        "emat_run_set_exp_pop_moves": [R, i32, P(_ExpPopSpecC)], "emat_run_exp_pop_moves": [R, P(_ExpPopResultC)], "emat_run_get_exp_pop": [R, P(dbl), P(dbl)],
         "emat_run_set_skygrid_moves": [R, i32, P(_SkygridSpecC)], "emat_run_skygrid_moves": [R, P(_SkygridResultC)], "emat_run_get_skygrid": [R, P(dbl), P(dbl)],
         "emat_run_set_site_rate_moves": [R, i32, dbl], "emat_run_site_rate_moves": [R, P(_SiteRateResultC)], "emat_run_get_site_rates": [R, P(dbl), P(dbl)],
     }
@@ -1186,6 +1255,23 @@ class EmatBackend:
         self._ck(self._lib.emat_tree_skygrid_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_tree_skygrid_moves")
         return SkygridMovesResult(res, gamma[:n], tr)
 
+    def exp_pop_moves(self, pop: PopModel, spec: "ExpPopSpec", t_ref: float, t_step: float, first_cell: int, k_bar, inner_t, key: int = 0, trace: bool = False) -> "ExpPopMovesResult":
+        """`spec.rounds` times pop_size_move + pop_growth_rate_move on the device (include/emat_backend.h: emat_exp_pop_moves), from the run's
+        statistics: the lineage grid k_bar over the cells first_cell .. and the inner nodes' times."""
+        kb = np.ascontiguousarray(k_bar, np.float64).reshape(-1); ts = np.ascontiguousarray(inner_t, np.float64).reshape(-1)
+        m = pop.c_struct(); sp = spec.c_struct(); dp = C.POINTER(C.c_double)
+        res, tr = _exp_pop_result_c(spec.rounds, trace)
+        self._ck(self._lib.emat_exp_pop_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(first_cell), kb.shape[0], kb.ctypes.data_as(dp),
+                                              ts.shape[0], ts.ctypes.data_as(dp), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_exp_pop_moves")
+        return ExpPopMovesResult._of(res, tr)
+
+    def tree_exp_pop_moves(self, pop: PopModel, spec: "ExpPopSpec", t_ref: float, t_step: float, key: int = 0, trace: bool = False) -> "ExpPopMovesResult":
+        """emat_exp_pop_moves on the statistics of the tree resident in HBM, which never leave it (emat_tree_exp_pop_moves)."""
+        m = pop.c_struct(); sp = spec.c_struct()
+        res, tr = _exp_pop_result_c(spec.rounds, trace)
+        self._ck(self._lib.emat_tree_exp_pop_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_tree_exp_pop_moves")
+        return ExpPopMovesResult._of(res, tr)
+
     def debug_pop_gradient(self, pop: PopModel, op: int, k: int, a, b) -> np.ndarray:
         """Test hook: the device's d log(integral of N over [a, b]) / d gamma_k (op 3) / d log N(a) / d gamma_k (op 4), point by point."""
         a = np.ascontiguousarray(a, np.float64); b = np.ascontiguousarray(b, np.float64); out = np.zeros_like(a)
@@ -1449,6 +1535,24 @@ class EmatRun:
         res, gamma, tr = _skygrid_result_c(n, getattr(self, "_sky_steps", 25), trace)
         self._ck(self._lib.emat_run_skygrid_moves(self._h, C.byref(res)), "emat_run_skygrid_moves")
         return SkygridMovesResult(res, gamma[:n], tr)
+
+    def set_exp_pop_moves(self, on: bool = True, spec: "ExpPopSpec" = None):
+        """The Exponential population moves once per cycle of do_mcmc_steps, before the repartition (off by default); `spec`: Run's settings of the two moves and the rounds."""
+        sp = (spec or ExpPopSpec()).c_struct()
+        self._ck(self._lib.emat_run_set_exp_pop_moves(self._h, 1 if on else 0, C.byref(sp)), "emat_run_set_exp_pop_moves")
+        self._xp_rounds = int(sp.rounds)
+
+    def exp_pop_moves(self, trace: bool = False) -> "ExpPopMovesResult":
+        """One call of the Exponential population moves on the assembled tree (emat_run_exp_pop_moves): `rounds` times the n0 step and the g step."""
+        res, tr = _exp_pop_result_c(getattr(self, "_xp_rounds", 0), trace)
+        self._ck(self._lib.emat_run_exp_pop_moves(self._h, C.byref(res)), "emat_run_exp_pop_moves")
+        return ExpPopMovesResult._of(res, tr)
+
+    def exp_pop(self):
+        """(n0, g) of the exponential population model as the driver holds them."""
+        n0, g = C.c_double(), C.c_double()
+        self._ck(self._lib.emat_run_get_exp_pop(self._h, C.byref(n0), C.byref(g)), "emat_run_get_exp_pop")
+        return n0.value, g.value
 
     def skygrid(self):
         """(gamma, tau) of the Skygrid curve as the driver holds them."""

@@ -693,6 +693,69 @@ emat_status emat_tree_coalescent_stats(emat_backend* h, double t_ref, double t_s
 emat_status emat_tree_skygrid_moves(emat_backend* h, const emat_pop_model* pop_model, const emat_skygrid_spec* spec, double t_ref, double t_step, uint64_t key, emat_skygrid_result* out);
 emat_status emat_debug_pop_gradient(emat_backend* h, const emat_pop_model* pop_model, int32_t op, int32_t k, int32_t n, const double* a, const double* b, double* out);
 
+/* ---- the Exponential population moves: n0 and the growth rate ----------------------------------------------------------------
+ * replaces: the Exp_pop_model branch of Run::run_global_moves (reference run.cpp:754-764): `rounds` times pop_size_move (:1237-1276)
+ * then pop_growth_rate_move (:1278-1319), on the device (csrc/emat_exp_pop_kernels.hpp).  Step s = 0 .. 2 rounds - 1 is a Metropolis step,
+ * even s on n0, odd s on g, and each re-evaluates Scalable_coalescent_prior::calc_log_prior (scalable_coalescent.cpp:140-187) under the
+ * proposed Exp_pop_model{t0, n0, g, min_pop}, its t_c derived afresh as the constructor derives it (pop_model.cpp:32-36), node by node:
+ * with the min_pop barrier log N(t) is not linear in (n0, g).
+ *
+ * Inputs are the statistics of the WHOLE run as emat_skygrid_moves takes them: the lineage grid k_bar[c] over the cells first_cell ..
+ * first_cell + num_cells - 1 and the times of the inner nodes.  A sharded caller adds the grids and concatenates the times.
+ * `pop_model` is the Exp_pop_model the steps start from.
+ *
+ * Each evaluation is one launch of G = min(256, ceil(max(num_inner, num_cells) / 1 024)) workgroups of 1 024 threads -- a function of the
+ * sizes only -- and each launch begins with every workgroup taking the previous step's decision from the same numbers; the host queues
+ * 1 + 2 rounds launches and one closing launch and synchronises once.  Every sum is added in a fixed order (thread, fixed tree over the
+ * workgroup, workgroups in order) and there are no atomics: the same arguments give the same result BIT FOR BIT on every handle and in
+ * every call.
+ *
+ * Random numbers: the (key, id) streams of the site-rate moves under the pseudo-id 0xFFFFFFF9, the next below the Skygrid's five.  Step s
+ * takes block s of that stream: word 0 the proposal's uniform, word 1 the acceptance uniform, both in [0, 1) and both drawn whether
+ * needed or not, so that a step's draws depend on (key, s) alone.
+ *   n0 step (:1249-1275)  scale = 0.75 + (1 / 0.75 - 0.75) u0, new_n0 = scale old_n0, log_prior_ratio = -(alpha + 1) log(scale)
+ *                         - beta (1 / new_n0 - 1 / old_n0), log_metropolis = (new - old log prior) + log_prior_ratio + log(old_n0 / new_n0).
+ *   g step (:1289-1318)   new_g = old_g + (-w + 2 w u0), w = 1 / 365; outside [g_min, g_max] the step ends at once (no evaluation, counted
+ *                         in g_out_of_bounds); log_prior_ratio = (|old_g - mu| - |new_g - mu|) / scale; no Hastings term.
+ *   both                  accepted when log_metropolis > 0 || u1 < exp(log_metropolis) (a NaN rejects); delta_log_other_priors grows by
+ *                         log_prior_ratio.  A disabled move's step does nothing but keeps its block.
+ *
+ * The call first finishes a pending pass.  It changes nothing in the handle.
+ * EMAT_ERR_INVALID_ARGUMENT (text in emat_last_error naming the first offender), all answered before the device is asked for: a null
+ * pointer; a model that is not EMAT_POP_EXP (the reference moves only Exp_pop_model, :1239); n0 not finite or <= 0; g or t0 not finite;
+ * min_pop negative or not finite; g_min > g_max or either NaN; g outside [g_min, g_max] (:1291); g_prior_scale not finite or <= 0;
+ * g_prior_mu or an inverse-gamma parameter not finite; rounds < 0; a trace with trace_capacity < 2 rounds; and emat_skygrid_moves'
+ * refusals of t_ref, t_step, num_cells, num_inner, k_bar and inner_t.  EMAT_ERR_CAPACITY: more than 2^22 cells, cell numbers outside
+ * [-2^30, 2^30), or rounds > 4 096.  EMAT_ERR_NO_DEVICE: a handle without a device, after the argument checks (there is no CPU path). */
+typedef struct emat_exp_pop_spec {          /* Run's setters, reference run.h:64-81, :206-211 */
+  int32_t n0_move_enabled, g_move_enabled;   /* final_pop_size_move_enabled_, pop_growth_rate_move_enabled_ */
+  double inv_n0_prior_alpha, inv_n0_prior_beta;   /* pop_inv_n0_prior_alpha_, _beta_; reference defaults 0, 0 */
+  double g_prior_mu, g_prior_scale, g_min, g_max;   /* pop_g_prior_mu_, ...; 0.001/365, 30.701135/365, -inf, +inf */
+  int32_t rounds, pad_;                      /* 50 in the reference (run.cpp:757); 0 = evaluate the prior only */
+} emat_exp_pop_spec;
+typedef struct emat_exp_pop_step {
+  double proposed;                           /* new_n0 (run.cpp:1252) or new_g (:1295); the value held when the move is disabled */
+  double log_coalescent_prior_proposed;      /* :1263, :1307; 0 when not evaluated */
+  double log_prior_ratio;                    /* :1255-1257, :1300-1301 */
+  double log_metropolis, u;                  /* :1265-1267, :1309-1310; u in [0, 1) */
+  int32_t accepted, evaluated;               /* evaluated = 0: the move is disabled or new_g left [g_min, g_max] (:1298) */
+} emat_exp_pop_step;
+typedef struct emat_exp_pop_result {
+  double n0, g;                              /* after the round */
+  double log_coalescent_prior_start;         /* calc_log_prior under the model passed in */
+  double log_coalescent_prior_end;           /* ... under the model returned (run.cpp:1269, :1312) */
+  double delta_log_other_priors;             /* :1270, :1313 of the steps accepted */
+  int32_t n0_accepted, g_accepted, g_out_of_bounds, pad_;
+  emat_exp_pop_step* trace;                  /* may be NULL: room for 2 * rounds records, step s at [s] */
+  int32_t trace_capacity;                    /* in: records `trace` has room for (>= 2 * rounds) */
+} emat_exp_pop_result;
+emat_status emat_exp_pop_moves(emat_backend* h, const emat_pop_model* pop_model, const emat_exp_pop_spec* spec, double t_ref, double t_step,
+                               int32_t first_cell, int32_t num_cells, const double* k_bar /*[num_cells]*/,
+                               int32_t num_inner, const double* inner_t /*[num_inner]*/, uint64_t key, emat_exp_pop_result* out);
+/* emat_exp_pop_moves on the statistics of the tree resident in HBM (emat_tree_coalescent_stats), which never leave it: bit for bit what
+ * emat_exp_pop_moves returns when fed the arrays that call hands out.  Its refusals are emat_exp_pop_moves' own, then the tree's state. */
+emat_status emat_tree_exp_pop_moves(emat_backend* h, const emat_pop_model* pop_model, const emat_exp_pop_spec* spec, double t_ref, double t_step, uint64_t key, emat_exp_pop_result* out);
+
 /* replaces: Run::calc_cur_log_coalescent_prior (reference run.cpp:455-465), i.e. Scalable_coalescent_prior::calc_log_prior
  * (scalable_coalescent.cpp:163-187) with every node displaced to its current time (:88-138): the whole-tree grid prior
  *   - sum_cells t_step kbar (kbar - 1) / (2 Nbar)  -  sum over inner nodes of log N(t),

@@ -235,6 +235,23 @@ emat_status emat_run_set_skygrid_moves(emat_run* r, int32_t on, const emat_skygr
 emat_status emat_run_skygrid_moves(emat_run* r, emat_skygrid_result* out /* may be NULL */);   /* needs the tree assembled */
 emat_status emat_run_get_skygrid(emat_run* r, double* gamma /*[knots]*/, double* tau /* either may be NULL */);
 
+/* The Exponential population moves of a run (Run::pop_size_move, pop_growth_rate_move, reference run.cpp:754-764, :1237-1319;
+ * emat_exp_pop_moves / emat_tree_exp_pop_moves of emat_backend.h).  Off by default: a run without them keeps the n0 and g of
+ * emat_run_set_pop_model for ever, and its cycle's code path is what it was.
+ *   emat_run_set_exp_pop_moves  on / off, and Run's settings for the two moves with the number of rounds (50 in the reference)
+ *                               (EMAT_ERR_INVALID_ARGUMENT: what emat_exp_pop_moves refuses in a spec).
+ *   emat_run_exp_pop_moves      one call of `rounds` rounds on the ASSEMBLED tree -- EMAT_ERR_STATE while the parts are out -- exactly as
+ *                               emat_run_skygrid_moves: emat_tree_exp_pop_moves with the tree in HBM, else the statistics made here and
+ *                               emat_exp_pop_moves; the same t_ref and t_step; the key of call k is the first word of Philox(counter k,
+ *                               key = run seed ^ a fixed tag of its own).  The accepted n0 and g become the run's, and the next repartition
+ *                               builds the parts' coalescent tables from them.  `out` (may be NULL): out->trace may be NULL.  A sharded run is
+ *                               refused as the site-rate moves refuse it; a model that is not exponential is EMAT_ERR_INVALID_ARGUMENT.
+ *   emat_run_get_exp_pop        n0 and g as the run holds them (either pointer may be NULL).
+ * With the group on, emat_run_do_mcmc_steps does one call at the top of every cycle, BEFORE the repartition, as for the Skygrid. */
+emat_status emat_run_set_exp_pop_moves(emat_run* r, int32_t on, const emat_exp_pop_spec* spec);
+emat_status emat_run_exp_pop_moves(emat_run* r, emat_exp_pop_result* out /* may be NULL */);   /* needs the tree assembled */
+emat_status emat_run_get_exp_pop(emat_run* r, double* n0, double* g /* either may be NULL */);
+
 /* repartition -> [push params, site-rate moves when on, local moves, reassemble] per cycle of `local_moves_per_cycle` moves
  * (<= 0: 50 x nodes, the reference default run.cpp:669-672), repartitioning at every cycle boundary. */
 emat_status emat_run_do_mcmc_steps(emat_run* r, int64_t steps, int64_t local_moves_per_cycle);
