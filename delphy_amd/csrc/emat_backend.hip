@@ -25,6 +25,7 @@
 #include <stdexcept>
 
 #include "../../include/emat_backend.h"
+#include "emat_move_specs.hpp"      // what the global moves' specs must satisfy (shared with the run driver)
 #include "emat_part_kernels.hpp"    // the per-part kernels, and the move headers they are compiled from
 #include "emat_host_model.hpp"
 #include "flat_tree.hpp"
@@ -641,5 +642,6 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 #include "emat_build_host.hpp"
 #include "emat_utree_host.hpp"
 #include "emat_site_rate_host.hpp"
+#include "emat_coal_stats_host.hpp"
 #include "emat_skygrid_host.hpp"
 #include "emat_exp_pop_host.hpp"

@@ -23,7 +23,8 @@
 #include <vector>
 
 #include "../../include/emat_host.h"
-#include "emat_gamma_pure.hpp"     // the generator the site-rate moves' key is drawn from
+#include "emat_gamma_pure.hpp"     // the generator the global moves' keys are drawn from
+#include "emat_move_specs.hpp"     // what their specs must satisfy, in the backend's words
 #include "flat_tree.hpp"
 #include "host_parallel.hpp"
 #include "synth.hpp"
@@ -421,9 +422,19 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // Run::alpha_moves + gibbs_sample_all_nus (run.cpp:1105-1235) on the device, from the statistics the device computes.
+  // ---- The global moves: three groups (site rates, Skygrid, Exponential population), one owner for each rule they share.
   static constexpr const char* kShardedStatistics = "a sharded run gathers the part lengths and sums S, R across ranks itself (see emat_backend.h)";
   static constexpr uint64_t kSiteRateKeyTag = 0x5349544552415445ull;   // "SITERATE"
+  // One round of a group: the key from the group's counter under its tag, the caller's trace buffer handed through, the counter bumped only when the backend did the round.
+  template <class Result, class Call> emat_status keyed_round(uint64_t& rounds, uint64_t tag, const Result* out, Result& res, Call&& call) {
+    uint32_t w[4]; philox4x32_10_pure(rounds, seed ^ tag, w);
+    if (out) { res.trace = out->trace; res.trace_capacity = out->trace_capacity; }
+    const emat_status st = bk(call((uint64_t)w[0] | ((uint64_t)w[1] << 32)));
+    if (st == EMAT_OK) ++rounds;
+    return st;
+  }
+
+  // Run::alpha_moves + gibbs_sample_all_nus (run.cpp:1105-1235) on the device, from the statistics the device computes.
   emat_status Ttwiddle_ext(const double* tree_length_of_part, int32_t* ext_offset, int32_t* ext_node, double* ext_length, int32_t capacity, int32_t* count);   // (both below, with the tree of parts)
   emat_status get_Ttwiddle_l(double* Ttwiddle_l);
   emat_status site_rate_moves(emat_site_rate_result* out) {
@@ -433,12 +444,8 @@ struct RunDriver {
     std::vector<double> Tt((size_t)L); std::vector<int32_t> M((size_t)L);
     EMAT_TRY(get_Ttwiddle_l(Tt.data()));
     EMAT_TRY(bk(emat_get_num_muts_l(backend, M.data())));
-    uint32_t w[4]; philox4x32_10_pure(site_rate_rounds, seed ^ kSiteRateKeyTag, w);
-    const uint64_t key = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
     emat_site_rate_result res{};
-    if (out) { res.trace = out->trace; res.trace_capacity = out->trace_capacity; }
-    EMAT_TRY(bk(emat_site_rate_moves(backend, Tt.data(), M.data(), site_rate_alpha, 10 /* run.cpp:1193 */, key, &res)));
-    ++site_rate_rounds;
+    EMAT_TRY(keyed_round(site_rate_rounds, kSiteRateKeyTag, out, res, [&](uint64_t key) { return emat_site_rate_moves(backend, Tt.data(), M.data(), site_rate_alpha, 10 /* run.cpp:1193 */, key, &res); }));
     // the backend holds the new rates already; kept here so that the next push sends the same values
     site_rate_alpha = res.alpha;
     nu_l.resize((size_t)L);
@@ -447,9 +454,11 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // Run::skygrid_tau_move + skygrid_gammas_zero_mode_gibbs_move + skygrid_gammas_hmc_move (run.cpp:766-778) on the device, on the ASSEMBLED tree: from
-  // the tree in HBM where it lives there, else from the two statistics made here from the host's tree (scalable_coalescent.cpp:88-138).
-  static constexpr uint64_t kSkygridKeyTag = 0x534B594752494431ull;   // "SKYGRID1"
+  // The population moves (run.cpp:754-778) run on the device, on the ASSEMBLED tree, in one process, on a model of their own kind: from the tree in HBM
+  // where it lives there, else from the two statistics made here from the host's tree (scalable_coalescent.cpp:88-138).
+  struct PopGroup { int32_t kind; const char* moves; const char* model; uint64_t tag; };
+  static constexpr PopGroup kSkygridGroup{EMAT_POP_SKYGRID, "the Skygrid moves", "a Skygrid population model", 0x534B594752494431ull};            // (the key's tag: "SKYGRID1")
+  static constexpr PopGroup kExpPopGroup{EMAT_POP_EXP, "the Exponential population moves", "an exponential population model", 0x455850504F503031ull};   // ("EXPPOP01")
   void host_tree_coalescent_stats(double t_ref, double ts, int32_t& first_cell, std::vector<double>& k_bar, std::vector<double>& inner_t) const {
     const auto cell = [&](double t) { return (int64_t)std::floor((t - t_ref) / ts); };
     double t_last = -INFINITY;
@@ -470,57 +479,42 @@ struct RunDriver {
       else if (n.parent != EMAT_NO_NODE) add(tree.nodes[(size_t)n.parent].t, cell(tree.nodes[(size_t)n.parent].t), n.t);
     }
   }
-  emat_status skygrid_moves(emat_skygrid_result* out) {
+  // One round of a population group: the preconditions, the statistics' source, the call (the backend's on the tree, or on statistics), the tail.  The group's caller writes the new parameters into the model.
+  template <class Spec, class Result, class OnTree, class OnStats>
+  emat_status pop_round(const PopGroup& g, uint64_t& rounds, const Spec& spec, Result* out, Result& res, OnTree on_tree, OnStats on_stats) {
     EMAT_TRY(need_backend());
-    if (tree_cut) return fail(EMAT_ERR_STATE, "the Skygrid moves need the tree assembled: reassemble first");
+    if (tree_cut) return fail(EMAT_ERR_STATE, std::string(g.moves) + " need the tree assembled: reassemble first");
     if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
     EMAT_TRY(need_pop_model());
-    if (pop.kind != EMAT_POP_SKYGRID) return fail(EMAT_ERR_INVALID_ARGUMENT, "the Skygrid moves need a Skygrid population model");
-    uint32_t w[4]; philox4x32_10_pure(skygrid_rounds, seed ^ kSkygridKeyTag, w);
-    const uint64_t key = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    std::vector<double> gamma(sky_g.size());
-    emat_skygrid_result res{};
-    res.gamma = gamma.data();
-    if (out) { res.trace = out->trace; res.trace_capacity = out->trace_capacity; }
+    if (pop.kind != g.kind) return fail(EMAT_ERR_INVALID_ARGUMENT, std::string(g.moves) + " need " + g.model);
     const emat_pop_model pm = pop_view();
     const double t_ref = tree.t_max_tip(), ts = coalescent_step();
-    if (device_tree && device_tree_uploaded) EMAT_TRY(bk(emat_tree_skygrid_moves(backend, &pm, &sky_spec, t_ref, ts, key, &res)));
-    else {
+    EMAT_TRY(keyed_round(rounds, g.tag, out, res, [&](uint64_t key) {
+      if (device_tree && device_tree_uploaded) return on_tree(backend, &pm, &spec, t_ref, ts, key, &res);
       int32_t first_cell = 0; std::vector<double> k_bar, inner_t;
       host_tree_coalescent_stats(t_ref, ts, first_cell, k_bar, inner_t);
-      EMAT_TRY(bk(emat_skygrid_moves(backend, &pm, &sky_spec, t_ref, ts, first_cell, (int32_t)k_bar.size(), k_bar.data(), (int32_t)inner_t.size(), inner_t.data(), key, &res)));
-    }
-    ++skygrid_rounds;
-    sky_g = gamma; sky_spec.tau = res.tau;
-    pop_model_changed();
-    if (out) { double* user_gamma = out->gamma; *out = res; out->gamma = user_gamma; if (user_gamma) std::copy(gamma.begin(), gamma.end(), user_gamma); }
-    return EMAT_OK;
-  }
-
-  // Run::pop_size_move + pop_growth_rate_move, xp_spec.rounds times (run.cpp:754-764), on the device, on the ASSEMBLED tree as the Skygrid moves.
-  static constexpr uint64_t kExpPopKeyTag = 0x455850504F503031ull;   // "EXPPOP01"
-  emat_status exp_pop_moves(emat_exp_pop_result* out) {
-    EMAT_TRY(need_backend());
-    if (tree_cut) return fail(EMAT_ERR_STATE, "the Exponential population moves need the tree assembled: reassemble first");
-    if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
-    EMAT_TRY(need_pop_model());
-    if (pop.kind != EMAT_POP_EXP) return fail(EMAT_ERR_INVALID_ARGUMENT, "the Exponential population moves need an exponential population model");
-    uint32_t w[4]; philox4x32_10_pure(exp_pop_rounds, seed ^ kExpPopKeyTag, w);
-    const uint64_t key = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    emat_exp_pop_result res{};
-    if (out) { res.trace = out->trace; res.trace_capacity = out->trace_capacity; }
-    const emat_pop_model pm = pop_view();
-    const double t_ref = tree.t_max_tip(), ts = coalescent_step();
-    if (device_tree && device_tree_uploaded) EMAT_TRY(bk(emat_tree_exp_pop_moves(backend, &pm, &xp_spec, t_ref, ts, key, &res)));
-    else {
-      int32_t first_cell = 0; std::vector<double> k_bar, inner_t;
-      host_tree_coalescent_stats(t_ref, ts, first_cell, k_bar, inner_t);
-      EMAT_TRY(bk(emat_exp_pop_moves(backend, &pm, &xp_spec, t_ref, ts, first_cell, (int32_t)k_bar.size(), k_bar.data(), (int32_t)inner_t.size(), inner_t.data(), key, &res)));
-    }
-    ++exp_pop_rounds;
-    pop.p[1] = res.n0; pop.p[2] = res.g;
+      return on_stats(backend, &pm, &spec, t_ref, ts, first_cell, (int32_t)k_bar.size(), k_bar.data(), (int32_t)inner_t.size(), inner_t.data(), key, &res);
+    }));
     pop_model_changed();
     if (out) *out = res;
+    return EMAT_OK;
+  }
+  // Run::skygrid_tau_move + skygrid_gammas_zero_mode_gibbs_move + skygrid_gammas_hmc_move (run.cpp:766-778)
+  emat_status skygrid_moves(emat_skygrid_result* out) {
+    std::vector<double> gamma(sky_g.size());
+    double* user_gamma = out ? out->gamma : nullptr;
+    emat_skygrid_result res{};
+    res.gamma = gamma.data();
+    EMAT_TRY(pop_round(kSkygridGroup, skygrid_rounds, sky_spec, out, res, emat_tree_skygrid_moves, emat_skygrid_moves));
+    sky_g = gamma; sky_spec.tau = res.tau;
+    if (out) { out->gamma = user_gamma; if (user_gamma) std::copy(gamma.begin(), gamma.end(), user_gamma); }   // (the curve goes to the caller's room, not the pointer to this one)
+    return EMAT_OK;
+  }
+  // Run::pop_size_move + pop_growth_rate_move, xp_spec.rounds times (run.cpp:754-764)
+  emat_status exp_pop_moves(emat_exp_pop_result* out) {
+    emat_exp_pop_result res{};
+    EMAT_TRY(pop_round(kExpPopGroup, exp_pop_rounds, xp_spec, out, res, emat_tree_exp_pop_moves, emat_exp_pop_moves));
+    pop.p[1] = res.n0; pop.p[2] = res.g;
     return EMAT_OK;
   }
 
@@ -804,6 +798,14 @@ emat_status emat::RunDriver::get_Ttwiddle_l(double* Ttwiddle_l) {
   EMAT_TRY(d.bk(emat_Ttwiddle_l_partial(d.backend, off.data(), node.data(), val.data(), S.data(), R.data(), &T)));
   return d.bk(emat_Ttwiddle_l_finish(d.backend, S.data(), R.data(), T, Ttwiddle_l));
 }
+// A population group's setter: the spec must pass the backend's own checks (emat_move_specs.hpp), refused in its words behind the setter's name `w`.
+template <class Spec, class Fault> emat_status set_moves_spec(emat_run* r, const std::string& w, int32_t on, const Spec* spec, Fault fault, bool emat::RunDriver::*is_on, Spec emat::RunDriver::*kept) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!spec) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, w + "spec must not be null");
+  if (const char* why = fault(*spec)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, w + why);
+  r->d.*is_on = on != 0; r->d.*kept = *spec;
+  return EMAT_OK;
+}
 extern "C" {
 emat_status emat_run_Ttwiddle_ext(emat_run* r, const double* tree_length_of_part, int32_t* ext_offset, int32_t* ext_node, double* ext_length, int32_t capacity, int32_t* count) {
   if (!r || !tree_length_of_part || !ext_offset || !count || capacity < 0 || (capacity > 0 && (!ext_node || !ext_length))) return EMAT_ERR_INVALID_ARGUMENT;
@@ -817,15 +819,7 @@ emat_status emat_run_set_site_rate_moves(emat_run* r, int32_t on, double alpha) 
 }
 emat_status emat_run_site_rate_moves(emat_run* r, emat_site_rate_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.site_rate_moves(out); }
 emat_status emat_run_set_skygrid_moves(emat_run* r, int32_t on, const emat_skygrid_spec* spec) {
-  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
-  if (!spec) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_skygrid_moves: spec must not be null");
-  const emat_skygrid_spec& s = *spec;
-  if (!std::isfinite(s.tau) || !(s.tau > 0.0)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_skygrid_moves: tau must be finite and positive");
-  if (s.low_gamma_barrier_enabled && (!std::isfinite(s.low_gamma_barrier_scale) || !(s.low_gamma_barrier_scale > 0.0)))
-    return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_skygrid_moves: low_gamma_barrier_scale must be finite and positive with the barrier on");
-  if (s.hmc_steps < 0 || !std::isfinite(s.hmc_mean_dt) || !(s.hmc_mean_dt > 0.0)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_skygrid_moves: hmc_steps must not be negative and hmc_mean_dt must be finite and positive");
-  r->d.skygrid_moves_on = on != 0; r->d.sky_spec = s;
-  return EMAT_OK;
+  return set_moves_spec(r, "emat_run_set_skygrid_moves: ", on, spec, [](const emat_skygrid_spec& s) { return skygrid_spec_fault(s); }, &RunDriver::skygrid_moves_on, &RunDriver::sky_spec);
 }
 emat_status emat_run_skygrid_moves(emat_run* r, emat_skygrid_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.skygrid_moves(out); }
 emat_status emat_run_get_skygrid(emat_run* r, double* gamma, double* tau) {
@@ -836,16 +830,7 @@ emat_status emat_run_get_skygrid(emat_run* r, double* gamma, double* tau) {
   return EMAT_OK;
 }
 emat_status emat_run_set_exp_pop_moves(emat_run* r, int32_t on, const emat_exp_pop_spec* spec) {
-  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
-  if (!spec) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: spec must not be null");
-  const emat_exp_pop_spec& s = *spec;
-  if (!(s.g_min <= s.g_max)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: g_min must not exceed g_max, and neither may be NaN");
-  if (!std::isfinite(s.g_prior_scale) || !(s.g_prior_scale > 0.0)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: g_prior_scale must be finite and positive");
-  if (!std::isfinite(s.g_prior_mu) || !std::isfinite(s.inv_n0_prior_alpha) || !std::isfinite(s.inv_n0_prior_beta))
-    return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: g_prior_mu, inv_n0_prior_alpha and inv_n0_prior_beta must be finite");
-  if (s.rounds < 0) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, "emat_run_set_exp_pop_moves: rounds must not be negative");
-  r->d.exp_pop_moves_on = on != 0; r->d.xp_spec = s;
-  return EMAT_OK;
+  return set_moves_spec(r, "emat_run_set_exp_pop_moves: ", on, spec, [](const emat_exp_pop_spec& s) { return exp_pop_spec_fault(s); }, &RunDriver::exp_pop_moves_on, &RunDriver::xp_spec);
 }
 emat_status emat_run_exp_pop_moves(emat_run* r, emat_exp_pop_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.exp_pop_moves(out); }
 emat_status emat_run_get_exp_pop(emat_run* r, double* n0, double* g) {

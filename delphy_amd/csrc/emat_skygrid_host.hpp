@@ -1,52 +1,46 @@
-// emat_skygrid_host.hpp -- the Skygrid population moves' entry points: emat_skygrid_moves, emat_tree_coalescent_stats, emat_tree_skygrid_moves and the gradient's test hook.
+// emat_skygrid_host.hpp -- the Skygrid population moves' entry points: emat_skygrid_moves, emat_tree_skygrid_moves and the gradient's test hook.
 //
-// Included by emat_backend.hip after emat_probe_host.hpp (probe_host_pop, probe_pop_table); the kernels: emat_skygrid_kernels.hpp.
+// Included by emat_backend.hip after emat_coal_stats_host.hpp (the statistics in h->coal, from the caller or from the tree in HBM); the kernels: emat_skygrid_kernels.hpp.
 #ifndef EMAT_SKYGRID_HOST_HPP_
 #define EMAT_SKYGRID_HOST_HPP_
 
 namespace {
 
-// The argument checks the two entry points share: the model, the spec, the grid's origin and the trace.  "" or EMAT_OK; `hp` receives the model.
-emat_status sky_check_model_and_spec(emat_backend* h, const std::string& w, const emat_pop_model* pm, const emat_skygrid_spec* spec, double t_ref, double t_step, const emat_skygrid_result* out, HostPopModel& hp) {
+// Both entry points: check the arguments (null pointers, the model, the grid's origin, the spec, the trace, the statistics handed in, the sizes), obtain the statistics
+// (`host`, or those of the tree in HBM where it is null), run.
+emat_status sky_moves(emat_backend* h, const std::string& w, const emat_pop_model* pm, const emat_skygrid_spec* spec, double t_ref, double t_step, const CoalHostStats* host, uint64_t key, emat_skygrid_result* out) {
+  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!pm || !spec || (host && (!host->k_bar || !host->inner_t)) || !out || !out->gamma) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "pop_model, spec, " + (host ? "k_bar, inner_t, " : "") + "out and out->gamma must not be null");
   if (pm->kind != EMAT_POP_SKYGRID) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "the population model is not a Skygrid");
+  HostPopModel hp;
   { const std::string why = probe_host_pop(*pm, hp); if (!why.empty()) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + why); }
   for (size_t k = 0; k < hp.gamma.size(); ++k)
     if (!std::isfinite(hp.gamma[k]) || !std::isfinite(hp.x[k])) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "knot " + std::to_string(k) + " has a time or a gamma that is not finite");
-  if (!std::isfinite(t_ref) || !std::isfinite(t_step) || !(t_step > 0.0)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "t_ref must be finite and t_step finite and positive");
-  const emat_skygrid_spec& s = *spec;
-  if (!std::isfinite(s.tau) || !(s.tau > 0.0)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "tau must be finite and positive");
-  if (s.low_gamma_barrier_enabled && (!std::isfinite(s.low_gamma_barrier_scale) || !(s.low_gamma_barrier_scale > 0.0)))
-    return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "low_gamma_barrier_scale must be finite and positive with the barrier on");
-  if (s.hmc_steps < 0) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "hmc_steps must not be negative");
-  if (!std::isfinite(s.hmc_mean_dt) || !(s.hmc_mean_dt > 0.0)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "hmc_mean_dt must be finite and positive");
-  if (out->trace && out->trace_capacity < s.hmc_steps) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "trace_capacity is smaller than hmc_steps");
-  return EMAT_OK;
-}
-emat_status sky_check_capacity(emat_backend* h, const std::string& w, size_t knots, int64_t first_cell, int64_t num_cells) {
-  if (knots > (size_t)k_sky_max_knots) return fail(h, EMAT_ERR_CAPACITY, w + std::to_string(knots) + " knots are more than the moves hold (" + std::to_string(k_sky_max_knots) + ")");
-  if (num_cells > k_sky_max_cells) return fail(h, EMAT_ERR_CAPACITY, w + std::to_string(num_cells) + " cells are more than the moves hold (" + std::to_string(k_sky_max_cells) + ")");
-  if (first_cell < -(1ll << 30) || first_cell + num_cells > (1ll << 30)) return fail(h, EMAT_ERR_CAPACITY, w + "the cells' numbers leave [-2^30, 2^30): choose t_ref nearer the tree");
-  return EMAT_OK;
-}
-
-// The two launches on statistics that are in h->sky.k_bar / h->sky.inner_t already; everything in the handle's own buffers.
-emat_status sky_run(emat_backend* h, const HostPopModel& hp, const emat_skygrid_spec& s, double t_ref, double t_step, int32_t first_cell, int32_t num_cells, int32_t num_inner,
-                    uint64_t key, emat_skygrid_result* out, HostLaps& laps) {
+  emat_status st = coal_check_origin(h, w, t_ref, t_step); if (st) return st;
+  if (const char* why = skygrid_spec_fault(*spec)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + why);
+  if (out->trace && out->trace_capacity < spec->hmc_steps) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "trace_capacity is smaller than hmc_steps");
+  st = coal_check_host_values(h, w, t_ref, t_step, host); if (st) return st;
+  if (hp.x.size() > (size_t)k_sky_max_knots) return fail(h, EMAT_ERR_CAPACITY, w + std::to_string(hp.x.size()) + " knots are more than the moves hold (" + std::to_string(k_sky_max_knots) + ")");
+  st = host ? coal_check_capacity(h, w, host->first_cell, host->num_cells) : EMAT_OK; if (st) return st;
+  HostLaps laps;   // (EMAT_VERBOSE=spans: the call by phase, each kernel waited for on its own)
+  st = coal_obtain(h, w, t_ref, t_step, host); if (st) return st;
+  // the two launches on the statistics in h->coal; everything in the handle's own buffers
   SkygridScratch& S = h->sky;
+  const CoalStatsScratch& K = h->coal;
   const size_t n = hp.x.size();
   const bool want_trace = out->trace != nullptr;
-  const size_t trace_doubles = want_trace ? (size_t)(k_sky_trace_head_rows + k_sky_trace_step_rows * s.hmc_steps) * n : 0;
+  const size_t trace_doubles = want_trace ? (size_t)(k_sky_trace_head_rows + k_sky_trace_step_rows * spec->hmc_steps) * n : 0;
   HIP_TRY(S.x.alloc(n)); HIP_TRY(S.g.alloc(n)); HIP_TRY(S.c.alloc(n)); HIP_TRY(S.W.alloc(n)); HIP_TRY(S.gamma_out.alloc(n));
-  HIP_TRY(S.popsize_bar.alloc_roomy((size_t)num_cells)); HIP_TRY(S.result.alloc((size_t)k_sky_result_doubles));
+  HIP_TRY(S.popsize_bar.alloc_roomy((size_t)K.num_cells)); HIP_TRY(S.result.alloc((size_t)k_sky_result_doubles));
   HIP_TRY(hipMemcpyAsync(S.x.p, hp.x.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(S.g.p, hp.gamma.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (want_trace) { HIP_TRY(S.trace.alloc_roomy(trace_doubles)); HIP_TRY(hipMemsetAsync(S.trace.p, 0, trace_doubles * sizeof(double), h->stream)); }
   SkygridArgs a{};
   a.type = hp.skygrid_type; a.num_knots = (int32_t)n; a.x = S.x.p; a.gamma_in = S.g.p;
   a.inv_dx = probe_pop_table(hp, S.x.p, S.g.p).skygrid_inv_dx;
-  a.t_ref = t_ref; a.t_step = t_step; a.first_cell = first_cell; a.num_cells = num_cells; a.k_bar = S.k_bar.p; a.popsize_bar = S.popsize_bar.p;
-  a.num_inner = num_inner; a.inner_t = S.inner_t.p; a.c_k = S.c.p; a.W_k = S.W.p;
-  a.spec = s; a.key = key; a.gamma_out = S.gamma_out.p; a.result = S.result.p; a.trace = want_trace ? S.trace.p : nullptr; a.trace_steps = want_trace ? s.hmc_steps : 0;
+  a.t_ref = t_ref; a.t_step = t_step; a.first_cell = K.first_cell; a.num_cells = K.num_cells; a.k_bar = K.k_bar.p; a.popsize_bar = S.popsize_bar.p;
+  a.num_inner = K.num_inner; a.inner_t = K.inner_t.p; a.c_k = S.c.p; a.W_k = S.W.p;
+  a.spec = *spec; a.key = key; a.gamma_out = S.gamma_out.p; a.result = S.result.p; a.trace = want_trace ? S.trace.p : nullptr; a.trace_steps = want_trace ? spec->hmc_steps : 0;
   laps.mark("skygrid_moves: 1 finish_pass, model and statistics to the device");
   hipLaunchKernelGGL(k_skygrid_node_stats, dim3((unsigned)n), dim3(k_sky_threads), 0, h->stream, a);
   HIP_TRY(hipGetLastError());
@@ -74,34 +68,6 @@ emat_status sky_run(emat_backend* h, const HostPopModel& hp, const emat_skygrid_
   return EMAT_OK;
 }
 
-// Scalable_coalescent_prior's grid and the inner nodes' times of the tree in HBM, into h->sky (k_bar, inner_t, first_cell, num_cells, num_inner).
-emat_status sky_tree_stats(emat_backend* h, const std::string& w, double t_ref, double t_step) {
-  emat_status st = gt_require_tree_home(h, false, w); if (st) return st;
-  GTreeHost& G = h->gt;
-  if (h->pass_pending) { st = finish_pass(h); if (st) return st; }
-  SkygridScratch& S = h->sky;
-  const GTreeDev T = G.dev();
-  HIP_TRY(S.extent.alloc(2)); HIP_TRY(S.count.alloc(1)); HIP_TRY(S.inner_t.alloc_roomy((size_t)G.n));
-  hipLaunchKernelGGL(k_skygrid_tree_extent, dim3(1), dim3(k_sky_threads), 0, h->stream, T, S.extent.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_skygrid_tree_inner_times, dim3(1), dim3(k_sky_threads), 0, h->stream, T, S.inner_t.p, S.count.p);
-  HIP_TRY(hipGetLastError());
-  double ext[2]; int32_t cnt = 0;
-  HIP_TRY(hipMemcpyAsync(ext, S.extent.p, sizeof ext, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&cnt, S.count.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  const double c_root = std::floor((ext[0] - t_ref) / t_step), c_tip = std::floor((ext[1] - t_ref) / t_step);   // Scalable_coalescent_prior::cell_for
-  if (!std::isfinite(c_root) || !std::isfinite(c_tip) || c_tip < c_root) return fail(h, EMAT_ERR_INTERNAL, w + "the resident tree's root is later than its latest tip");
-  const double cells = c_tip - c_root + 1.0;
-  if (cells > (double)k_sky_max_cells) return fail(h, EMAT_ERR_CAPACITY, w + std::to_string((long long)cells) + " cells are more than the moves hold (" + std::to_string(k_sky_max_cells) + ")");
-  if (c_root < -(double)(1 << 30) || c_tip >= (double)(1 << 30)) return fail(h, EMAT_ERR_CAPACITY, w + "the cells' numbers leave [-2^30, 2^30): choose t_ref nearer the tree");
-  S.first_cell = (int32_t)c_root; S.num_cells = (int32_t)cells; S.num_inner = cnt;
-  HIP_TRY(S.k_bar.alloc_roomy((size_t)S.num_cells));
-  hipLaunchKernelGGL(k_skygrid_tree_k_bar, dim3((unsigned)S.num_cells), dim3(k_sky_threads), 0, h->stream, T, t_ref, t_step, S.first_cell, S.num_cells, S.k_bar.p);
-  HIP_TRY(hipGetLastError());
-  return EMAT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -109,67 +75,13 @@ extern "C" {
 /* skygrid_tau_move + skygrid_gammas_zero_mode_gibbs_move + skygrid_gammas_hmc_move on the device (header: emat_skygrid_moves) */
 emat_status emat_skygrid_moves(emat_backend* h, const emat_pop_model* pm, const emat_skygrid_spec* spec, double t_ref, double t_step, int32_t first_cell, int32_t num_cells,
                                const double* k_bar, int32_t num_inner, const double* inner_t, uint64_t key, emat_skygrid_result* out) {
-  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
-  const std::string w = "emat_skygrid_moves: ";
-  if (!pm || !spec || !k_bar || !inner_t || !out || !out->gamma) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "pop_model, spec, k_bar, inner_t, out and out->gamma must not be null");
-  HostPopModel hp;
-  emat_status st = sky_check_model_and_spec(h, w, pm, spec, t_ref, t_step, out, hp); if (st) return st;
-  if (num_cells < 1) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "num_cells must be at least 1");
-  if (num_inner < 1) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "num_inner must be at least 1");
-  for (int32_t c = 0; c < num_cells; ++c)
-    if (!std::isfinite(k_bar[c]) || k_bar[c] < 0.0) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "k_bar of cell " + std::to_string(c) + " is negative or not finite");
-  for (int32_t i = 0; i < num_inner; ++i) {
-    if (!std::isfinite(inner_t[i])) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "inner_t of node " + std::to_string(i) + " is not finite");
-    const double cell = std::floor((inner_t[i] - t_ref) / t_step);   // Scalable_coalescent_prior::cell_for
-    if (cell < (double)first_cell || cell >= (double)first_cell + (double)num_cells) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "inner_t of node " + std::to_string(i) + " lies outside the grid");
-  }
-  st = sky_check_capacity(h, w, hp.x.size(), first_cell, num_cells); if (st) return st;
-  if (h->host_only) return no_device(h);
-  if (!bind_device(h)) return fail(h, EMAT_ERR_HIP, "hipSetDevice failed");
-  HostLaps laps;   // (EMAT_VERBOSE=spans: the call by phase, each kernel waited for on its own)
-  if (h->pass_pending) { st = finish_pass(h); if (st) return st; }
-  SkygridScratch& S = h->sky;
-  HIP_TRY(S.k_bar.alloc_roomy((size_t)num_cells)); HIP_TRY(S.inner_t.alloc_roomy((size_t)num_inner));
-  HIP_TRY(hipMemcpyAsync(S.k_bar.p, k_bar, (size_t)num_cells * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(S.inner_t.p, inner_t, (size_t)num_inner * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  return sky_run(h, hp, *spec, t_ref, t_step, first_cell, num_cells, num_inner, key, out, laps);
-}
-
-/* the whole-tree statistics of the tree in HBM (header: emat_tree_coalescent_stats) */
-emat_status emat_tree_coalescent_stats(emat_backend* h, double t_ref, double t_step, int32_t* first_cell, int32_t* num_cells, double* k_bar, int32_t k_bar_capacity,
-                                       double* inner_t, int32_t inner_capacity, int32_t* num_inner) {
-  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
-  const std::string w = "emat_tree_coalescent_stats: ";
-  if (!first_cell || !num_cells || !num_inner) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "first_cell, num_cells and num_inner must not be null");
-  if (!std::isfinite(t_ref) || !std::isfinite(t_step) || !(t_step > 0.0)) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "t_ref must be finite and t_step finite and positive");
-  emat_status st = sky_tree_stats(h, w, t_ref, t_step); if (st) return st;
-  SkygridScratch& S = h->sky;
-  *first_cell = S.first_cell; *num_cells = S.num_cells; *num_inner = S.num_inner;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (k_bar) {
-    if (k_bar_capacity < S.num_cells) return fail(h, EMAT_ERR_BUFFER_TOO_SMALL, w + std::to_string(S.num_cells) + " cells, room for " + std::to_string(k_bar_capacity));
-    HIP_TRY(hipMemcpy(k_bar, S.k_bar.p, (size_t)S.num_cells * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  if (inner_t) {
-    if (inner_capacity < S.num_inner) return fail(h, EMAT_ERR_BUFFER_TOO_SMALL, w + std::to_string(S.num_inner) + " inner nodes, room for " + std::to_string(inner_capacity));
-    HIP_TRY(hipMemcpy(inner_t, S.inner_t.p, (size_t)S.num_inner * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  return EMAT_OK;
+  const CoalHostStats host{first_cell, num_cells, k_bar, num_inner, inner_t};
+  return sky_moves(h, "emat_skygrid_moves: ", pm, spec, t_ref, t_step, &host, key, out);
 }
 
 /* the moves on the statistics of the tree in HBM, which never leave it (header: emat_tree_skygrid_moves) */
 emat_status emat_tree_skygrid_moves(emat_backend* h, const emat_pop_model* pm, const emat_skygrid_spec* spec, double t_ref, double t_step, uint64_t key, emat_skygrid_result* out) {
-  if (!h) return EMAT_ERR_INVALID_ARGUMENT;
-  const std::string w = "emat_tree_skygrid_moves: ";
-  if (!pm || !spec || !out || !out->gamma) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "pop_model, spec, out and out->gamma must not be null");
-  HostPopModel hp;
-  emat_status st = sky_check_model_and_spec(h, w, pm, spec, t_ref, t_step, out, hp); if (st) return st;
-  st = sky_check_capacity(h, w, hp.x.size(), 0, 1); if (st) return st;
-  HostLaps laps;
-  st = sky_tree_stats(h, w, t_ref, t_step); if (st) return st;
-  SkygridScratch& S = h->sky;
-  if (S.num_inner < 1) return fail(h, EMAT_ERR_INVALID_ARGUMENT, w + "the resident tree has no inner node");
-  return sky_run(h, hp, *spec, t_ref, t_step, S.first_cell, S.num_cells, S.num_inner, key, out, laps);
+  return sky_moves(h, "emat_tree_skygrid_moves: ", pm, spec, t_ref, t_step, nullptr, key, out);
 }
 
 /* test hook (header: emat_debug_pop_gradient) */

@@ -157,18 +157,28 @@ struct GTreeHost {
   GPools pools() { GPools q{}; q.muts = pool_muts.p; q.ivs = pool_ivs.p; q.mut_cap = (uint32_t)pool_muts.n; q.iv_cap = (uint32_t)pool_ivs.n; q.tops = pool_tops.p; return q; }
 };
 
-// What the Skygrid population moves work in (emat_skygrid_kernels.hpp, emat_skygrid_host.hpp): grow-only, kept from call to call.  k_bar, inner_t and the
-// grid's numbers are also where emat_tree_coalescent_stats leaves the tree's statistics for emat_tree_skygrid_moves.
-struct SkygridScratch {
-  DevBuf<double> x, g, k_bar, popsize_bar, inner_t, c, W, gamma_out, result, trace, extent;
+// The whole-tree coalescent statistics both population groups read (emat_coal_stats_host.hpp), from the caller or from the tree in HBM, and their grid: grow-only, the numbers are the last call's.
+struct CoalStatsScratch {
+  DevBuf<double> k_bar, inner_t, extent;
   DevBuf<int32_t> count;
   int32_t first_cell = 0, num_cells = 0, num_inner = 0;
 };
 
-// What the Exponential population moves work in beyond the statistics in SkygridScratch (emat_exp_pop_kernels.hpp, emat_exp_pop_host.hpp): grow-only.
+// What the Skygrid population moves work in (emat_skygrid_kernels.hpp, emat_skygrid_host.hpp): grow-only, kept from call to call.
+struct SkygridScratch {
+  DevBuf<double> x, g, popsize_bar, c, W, gamma_out, result, trace;
+};
+
+// What the Exponential population moves work in (emat_exp_pop_kernels.hpp, emat_exp_pop_host.hpp): grow-only.
 struct ExpPopScratch {
   DevBuf<double> state, partials, result;
   DevBuf<emat_exp_pop_step> trace;
+};
+
+// What the site-rate moves work in (emat_site_rate_kernels.hpp, emat_site_rate_host.hpp): grow-only, sized by the handle's L at the first call.
+struct SiteRateScratch {
+  DevBuf<double> T, nu_new, d_log_G, d_prior, result; DevBuf<int32_t> M;
+  DevBuf<emat_site_rate_step> trace;
 };
 
 // Scratch of the tree probers (emat_probe_kernels.hpp, emat_probe_host.hpp), one set for the resident tree and for the samples of the store:
@@ -301,8 +311,10 @@ struct emat_backend {
   DevBuf<uint8_t> d_headers; std::vector<uint8_t> h_headers; bool headers_current = false;
   GTreeHost gt;                     // the whole tree, when it lives in HBM (emat_tree_upload)
   ProbeScratch probe;               // what emat_tree_probe_* / emat_tree_branch_counts work in
-  SkygridScratch sky;               // what emat_skygrid_moves / emat_tree_coalescent_stats work in
+  CoalStatsScratch coal;            // the statistics the population moves read (emat_tree_coalescent_stats, or uploaded by the caller)
+  SkygridScratch sky;               // what emat_skygrid_moves works in
   ExpPopScratch xp;                 // what emat_exp_pop_moves works in
+  SiteRateScratch sr;               // what emat_site_rate_moves works in
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
   int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs

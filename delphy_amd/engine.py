@@ -10,7 +10,7 @@ import ctypes as C
 import math
 import os
 import subprocess
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 from typing import Optional, Sequence
 
 import numpy as np
@@ -101,6 +101,12 @@ class _SiteRateResultC(C.Structure):
 
 
 SITE_RATE_STEP_DTYPE = np.dtype([("proposed_alpha", "f8"), ("log_p_proposed", "f8"), ("log_metropolis", "f8"), ("u", "f8"), ("accepted", "i4"), ("pad_", "i4")])
+_SITE_RATE_TRACE = (_SiteRateResultC, _SiteRateStepC, SITE_RATE_STEP_DTYPE)   # what _traced_result_c makes a site-rate result of
+
+
+def _traced_result(cls, res, trace):
+    """A result dataclass of the global moves from its C struct: the struct's scalars under their names, in its order, then the trace."""
+    return cls(*[getattr(res, f.name) for f in fields(cls)[:-1]], trace)
 
 
 @dataclass
@@ -117,18 +123,17 @@ class SiteRateResult:
     sum_nu_new: float
     trace: Optional[np.ndarray]    # [num_alpha_steps] records of SITE_RATE_STEP_DTYPE, or None when not asked for
 
-    @staticmethod
-    def _of(res: "_SiteRateResultC", trace):
-        return SiteRateResult(res.alpha, res.log_p_alpha_start, res.num_accepted, res.num_floored, res.delta_log_G, res.delta_log_prior_alpha,
-                              res.delta_log_prior_nu, res.sum_nu_old, res.sum_nu_new, trace)
+
+_KEY_MASK = 0xFFFFFFFFFFFFFFFF   # a move key as the C ABI takes it: the low 64 bits
 
 
-def _site_rate_result_c(num_steps: int, trace: bool):
-    res = _SiteRateResultC()
-    tr = np.zeros(max(1, num_steps), SITE_RATE_STEP_DTYPE) if trace else None
+def _traced_result_c(result_c, step_c, dtype, steps: int, trace: bool):
+    """(a C result of the global moves with room for `steps` trace records when they are asked for, those records or None)."""
+    res = result_c(); steps = max(0, int(steps))
+    tr = np.zeros(max(1, steps), dtype) if trace else None
     if trace:
-        res.trace = tr.ctypes.data_as(C.POINTER(_SiteRateStepC)); res.trace_capacity = num_steps
-    return res, tr
+        res.trace = tr.ctypes.data_as(C.POINTER(step_c)); res.trace_capacity = steps
+    return res, (None if tr is None else tr[:steps])
 
 
 class _SkygridSpecC(C.Structure):
@@ -221,6 +226,7 @@ class _ExpPopResultC(C.Structure):
 
 EXP_POP_STEP_DTYPE = np.dtype([("proposed", "f8"), ("log_coalescent_prior_proposed", "f8"), ("log_prior_ratio", "f8"), ("log_metropolis", "f8"), ("u", "f8"),
                                ("accepted", "i4"), ("evaluated", "i4")])
+_EXP_POP_TRACE = (_ExpPopResultC, _ExpPopStepC, EXP_POP_STEP_DTYPE)   # ... and one of the Exponential population moves (steps = 2 * rounds)
 
 
 @dataclass
@@ -253,20 +259,6 @@ class ExpPopMovesResult:
     g_accepted: int
     g_out_of_bounds: int
     trace: Optional[np.ndarray]    # [2 * rounds] records of EXP_POP_STEP_DTYPE (even: n0 steps, odd: g steps), or None when not asked for
-
-    @staticmethod
-    def _of(res: "_ExpPopResultC", trace):
-        return ExpPopMovesResult(res.n0, res.g, res.log_coalescent_prior_start, res.log_coalescent_prior_end, res.delta_log_other_priors,
-                                 res.n0_accepted, res.g_accepted, res.g_out_of_bounds, trace)
-
-
-def _exp_pop_result_c(rounds: int, trace: bool):
-    res = _ExpPopResultC()
-    steps = 2 * max(0, int(rounds))
-    tr = np.zeros(max(1, steps), EXP_POP_STEP_DTYPE) if trace else None
-    if trace:
-        res.trace = tr.ctypes.data_as(C.POINTER(_ExpPopStepC)); res.trace_capacity = steps
-    return res, (None if tr is None else tr[:steps])
 
 
 @dataclass
@@ -1223,19 +1215,26 @@ class EmatBackend:
         T = np.ascontiguousarray(Ttwiddle_l, np.float64); M = np.ascontiguousarray(num_muts_l, np.int32)
         if T.shape != (self.num_sites,) or M.shape != (self.num_sites,):
             raise ValueError("Ttwiddle_l and num_muts_l must have one entry per site")
-        res, tr = _site_rate_result_c(int(num_alpha_steps), trace and num_alpha_steps > 0)
+        res, tr = _traced_result_c(*_SITE_RATE_TRACE, int(num_alpha_steps), trace and num_alpha_steps > 0)
         self._ck(self._lib.emat_site_rate_moves(self._h, T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int32)), float(alpha), int(num_alpha_steps),
-                                                int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_site_rate_moves")
-        return SiteRateResult._of(res, None if tr is None else tr[:num_alpha_steps])
+                                                int(key) & _KEY_MASK, C.byref(res)), "emat_site_rate_moves")
+        return _traced_result(SiteRateResult, res, tr)
+
+    def _pop_moves(self, name: str, pop: PopModel, spec, t_ref: float, t_step: float, first_cell: int, k_bar, inner_t, key: int, res):
+        """A population group's call emat_<name> on the statistics handed in, or emat_tree_<name> on the resident tree's own where `k_bar` is None."""
+        m = pop.c_struct(); sp = spec.c_struct(); dp = C.POINTER(C.c_double); stats = ()
+        if k_bar is not None:
+            kb = np.ascontiguousarray(k_bar, np.float64).reshape(-1); ts = np.ascontiguousarray(inner_t, np.float64).reshape(-1)
+            stats = (int(first_cell), kb.shape[0], kb.ctypes.data_as(dp), ts.shape[0], ts.ctypes.data_as(dp))
+        name = ("emat_tree_" if k_bar is None else "emat_") + name
+        self._ck(getattr(self._lib, name)(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), *stats, int(key) & _KEY_MASK, C.byref(res)), name)
 
     def skygrid_moves(self, pop: PopModel, spec: "SkygridSpec", t_ref: float, t_step: float, first_cell: int, k_bar, inner_t, key: int = 0, trace: bool = False) -> "SkygridMovesResult":
         """skygrid_tau_move + the zero mode's Gibbs move + the HMC on the gammas, on the device (include/emat_backend.h: emat_skygrid_moves), from the
         run's statistics: the lineage grid k_bar over the cells first_cell .. and the inner nodes' times."""
-        kb = np.ascontiguousarray(k_bar, np.float64).reshape(-1); ts = np.ascontiguousarray(inner_t, np.float64).reshape(-1)
-        m = pop.c_struct(); sp = spec.c_struct(); n = int(m.skygrid_num_knots); dp = C.POINTER(C.c_double)
+        n = int(pop.c_struct().skygrid_num_knots)
         res, gamma, tr = _skygrid_result_c(n, spec.hmc_steps, trace)
-        self._ck(self._lib.emat_skygrid_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(first_cell), kb.shape[0], kb.ctypes.data_as(dp),
-                                              ts.shape[0], ts.ctypes.data_as(dp), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_skygrid_moves")
+        self._pop_moves("skygrid_moves", pop, spec, t_ref, t_step, first_cell, k_bar, inner_t, key, res)
         return SkygridMovesResult(res, gamma[:n], tr)
 
     def tree_coalescent_stats(self, t_ref: float, t_step: float):
@@ -1250,27 +1249,18 @@ class EmatBackend:
 
     def tree_skygrid_moves(self, pop: PopModel, spec: "SkygridSpec", t_ref: float, t_step: float, key: int = 0, trace: bool = False) -> "SkygridMovesResult":
         """emat_skygrid_moves on the statistics of the tree resident in HBM, which never leave it (emat_tree_skygrid_moves)."""
-        m = pop.c_struct(); sp = spec.c_struct(); n = int(m.skygrid_num_knots)
-        res, gamma, tr = _skygrid_result_c(n, spec.hmc_steps, trace)
-        self._ck(self._lib.emat_tree_skygrid_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_tree_skygrid_moves")
-        return SkygridMovesResult(res, gamma[:n], tr)
+        return self.skygrid_moves(pop, spec, t_ref, t_step, 0, None, None, key, trace)
 
     def exp_pop_moves(self, pop: PopModel, spec: "ExpPopSpec", t_ref: float, t_step: float, first_cell: int, k_bar, inner_t, key: int = 0, trace: bool = False) -> "ExpPopMovesResult":
         """`spec.rounds` times pop_size_move + pop_growth_rate_move on the device (include/emat_backend.h: emat_exp_pop_moves), from the run's
         statistics: the lineage grid k_bar over the cells first_cell .. and the inner nodes' times."""
-        kb = np.ascontiguousarray(k_bar, np.float64).reshape(-1); ts = np.ascontiguousarray(inner_t, np.float64).reshape(-1)
-        m = pop.c_struct(); sp = spec.c_struct(); dp = C.POINTER(C.c_double)
-        res, tr = _exp_pop_result_c(spec.rounds, trace)
-        self._ck(self._lib.emat_exp_pop_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(first_cell), kb.shape[0], kb.ctypes.data_as(dp),
-                                              ts.shape[0], ts.ctypes.data_as(dp), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_exp_pop_moves")
-        return ExpPopMovesResult._of(res, tr)
+        res, tr = _traced_result_c(*_EXP_POP_TRACE, 2 * spec.rounds, trace)
+        self._pop_moves("exp_pop_moves", pop, spec, t_ref, t_step, first_cell, k_bar, inner_t, key, res)
+        return _traced_result(ExpPopMovesResult, res, tr)
 
     def tree_exp_pop_moves(self, pop: PopModel, spec: "ExpPopSpec", t_ref: float, t_step: float, key: int = 0, trace: bool = False) -> "ExpPopMovesResult":
         """emat_exp_pop_moves on the statistics of the tree resident in HBM, which never leave it (emat_tree_exp_pop_moves)."""
-        m = pop.c_struct(); sp = spec.c_struct()
-        res, tr = _exp_pop_result_c(spec.rounds, trace)
-        self._ck(self._lib.emat_tree_exp_pop_moves(self._h, C.byref(m), C.byref(sp), float(t_ref), float(t_step), int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(res)), "emat_tree_exp_pop_moves")
-        return ExpPopMovesResult._of(res, tr)
+        return self.exp_pop_moves(pop, spec, t_ref, t_step, 0, None, None, key, trace)
 
     def debug_pop_gradient(self, pop: PopModel, op: int, k: int, a, b) -> np.ndarray:
         """Test hook: the device's d log(integral of N over [a, b]) / d gamma_k (op 3) / d log N(a) / d gamma_k (op 4), point by point."""
@@ -1288,7 +1278,7 @@ class EmatBackend:
     def debug_sample_gamma(self, key: int, n: int, shape: float, rate: float) -> np.ndarray:
         """Test hook: n draws of the site-rate moves' gamma sampler, draw i from the stream (key, i)."""
         out = np.zeros(max(0, int(n)))
-        self._ck(self._lib.emat_debug_sample_gamma(self._h, int(key) & 0xFFFFFFFFFFFFFFFF, int(n), float(shape), float(rate), out.ctypes.data_as(C.POINTER(C.c_double))), "emat_debug_sample_gamma")
+        self._ck(self._lib.emat_debug_sample_gamma(self._h, int(key) & _KEY_MASK, int(n), float(shape), float(rate), out.ctypes.data_as(C.POINTER(C.c_double))), "emat_debug_sample_gamma")
         return out
 
     def debug_gamma(self, mode: int, a, x_or_q) -> np.ndarray:
@@ -1519,9 +1509,9 @@ class EmatRun:
 
     def site_rate_moves(self, trace: bool = False) -> "SiteRateResult":
         """One round of site-rate moves while the parts are out (emat_run_site_rate_moves): ten alpha steps and the draw of every nu_l."""
-        res, tr = _site_rate_result_c(10, trace)
+        res, tr = _traced_result_c(*_SITE_RATE_TRACE, 10, trace)
         self._ck(self._lib.emat_run_site_rate_moves(self._h, C.byref(res)), "emat_run_site_rate_moves")
-        return SiteRateResult._of(res, tr)
+        return _traced_result(SiteRateResult, res, tr)
 
     def set_skygrid_moves(self, on: bool = True, spec: "SkygridSpec" = None):
         """The Skygrid population moves once per cycle of do_mcmc_steps, before the repartition (off by default); `spec`: Run's Skygrid settings and the tau to start from."""
@@ -1544,9 +1534,9 @@ class EmatRun:
 
     def exp_pop_moves(self, trace: bool = False) -> "ExpPopMovesResult":
         """One call of the Exponential population moves on the assembled tree (emat_run_exp_pop_moves): `rounds` times the n0 step and the g step."""
-        res, tr = _exp_pop_result_c(getattr(self, "_xp_rounds", 0), trace)
+        res, tr = _traced_result_c(*_EXP_POP_TRACE, 2 * getattr(self, "_xp_rounds", 0), trace)
         self._ck(self._lib.emat_run_exp_pop_moves(self._h, C.byref(res)), "emat_run_exp_pop_moves")
-        return ExpPopMovesResult._of(res, tr)
+        return _traced_result(ExpPopMovesResult, res, tr)
 
     def exp_pop(self):
         """(n0, g) of the exponential population model as the driver holds them."""
