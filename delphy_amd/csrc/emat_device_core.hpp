@@ -315,7 +315,8 @@ EMAT_D double uniform_co(Ctx& c, double lo, double hi) { return lo + (hi - lo) *
 EMAT_D double uniform_oc(Ctx& c, double lo, double hi) { return lo + (hi - lo) * u01_oc(c); }
 // floor(x n / 2^64) of the next word x, for n >= 1 (every caller: a node count, a list length, 3).  The sign-extended n costs four
 // multiplies where (uint32_t)n would take two; that spelling measured inside the run-to-run spread and was not kept.
-EMAT_D int uniform_int(Ctx& c, int n) { return (int)__umul64hi(rng_next64(c), (uint64_t)n); }
+EMAT_DF int uniform_pick(uint64_t x, int n) { return (int)__umul64hi(x, (uint64_t)n); }   // (of a word already taken: the chain's frame, settle_moves)
+EMAT_D int uniform_int(Ctx& c, int n) { return uniform_pick(rng_next64(c), n); }
 EMAT_D double gaussian(Ctx& c, double mean, double sigma) {
   uint64_t a = rng_next64(c), b = rng_next64(c);
   double u1 = to_oc(a), u2 = to_co(b);

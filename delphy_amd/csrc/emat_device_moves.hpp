@@ -164,10 +164,11 @@ template <bool kRoot> EMAT_DF void inner_node_displace_body(Ctx& c, ByteCount& n
 }
 template <bool kRoot> EMAT_NOTAIL EMAT_DN void inner_node_displace_move(Ctx& c) { EMAT_TIMED(2); ByteCount n; inner_node_displace_body<kRoot>(c, n); count_bytes(c, n); }
 
-template <bool kRoot> EMAT_DF void tip_displace_body(Ctx& c, ByteCount& n) {   // subrun.cpp:234-285
-  begin_move(c, k_tip_displace);
-  int node;
-  { int guard = 0; do { node = pick_random_node(c); } while (!is_tip(c, node) && guard++ < (1 << 26)); }
+// The tip displacement and the branch reform each have two entries.  The first draws the move's node and forwards; the second takes a
+// node the chain's frame has drawn already (settle_moves, below) and draws nothing for the pick, so every later draw stands where it
+// stood in the stream.  The bodies exist once.
+EMAT_DF int pick_random_tip(Ctx& c) { int node; int guard = 0; do { node = pick_random_node(c); } while (!is_tip(c, node) && guard++ < (1 << 26)); return node; }
+template <bool kRoot> EMAT_DF void tip_displace_body(Ctx& c, ByteCount& n, int node) {   // subrun.cpp:234-285
   c.tr_node = node;
   const NodeRec nd = nodes_of(c)[node];
   if (nd.t_min == nd.t_max) return;
@@ -195,7 +196,8 @@ template <bool kRoot> EMAT_DF void tip_displace_body(Ctx& c, ByteCount& n) {   /
     hdr_of(c)->log_aug_prior += delta_log_prior;
   }
 }
-template <bool kRoot> EMAT_NOTAIL EMAT_DN void tip_displace_move(Ctx& c) { EMAT_TIMED(2); ByteCount n; tip_displace_body<kRoot>(c, n); count_bytes(c, n); }
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void tip_displace_move(Ctx& c) { EMAT_TIMED(2); ByteCount n; begin_move(c, k_tip_displace); tip_displace_body<kRoot>(c, n, pick_random_tip(c)); count_bytes(c, n); }
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void tip_displace_move_picked(Ctx& c, int node) { EMAT_TIMED(2); ByteCount n; begin_move(c, k_tip_displace); tip_displace_body<kRoot>(c, n, node); count_bytes(c, n); }
 
 // phylo_tree.cpp:579-644; result in scratch
 EMAT_DF SVec<MutRec> randomize_branch_mutation_times(Ctx& c, int X) { EMAT_TIMED(2);
@@ -314,10 +316,7 @@ template <int N> EMAT_DN int branch_reform_small(Ctx& c, int X, double lam, doub
 #ifndef EMAT_REFORM_SMALL_MAX
 #define EMAT_REFORM_SMALL_MAX 4
 #endif
-template <bool kRoot> EMAT_DF void branch_reform_body(Ctx& c, ByteCount& n_bytes) {   // subrun.cpp:287-320
-  begin_move(c, k_branch_reform);
-  if (hdr_of(c)->n_nodes < 3) return;
-  const int X = pick_random_node(c);
+template <bool kRoot> EMAT_DF void branch_reform_body(Ctx& c, ByteCount& n_bytes, int X) {   // subrun.cpp:287-320, from the pick on
   c.tr_node = X;
   if (X == hdr_of(c)->root) return;
   const int P = nodes_of(c)[X].parent;
@@ -374,7 +373,13 @@ template <bool kRoot> EMAT_DF void branch_reform_body(Ctx& c, ByteCount& n_bytes
     list_assign<MutRec>(c, nodes_of(c)[X].muts, nm.p, nm.n); hdr_of(c)->log_G += delta_log_G; n_bytes.all += 16 * nm.n; n_bytes.written += 16 * nm.n;
   }
 }
-template <bool kRoot> EMAT_NOTAIL EMAT_DN void branch_reform_move(Ctx& c) { EMAT_TIMED(2); ByteCount n; branch_reform_body<kRoot>(c, n); count_bytes(c, n); }
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void branch_reform_move(Ctx& c) { EMAT_TIMED(2);
+  ByteCount n;
+  begin_move(c, k_branch_reform);
+  if (hdr_of(c)->n_nodes >= 3) branch_reform_body<kRoot>(c, n, pick_random_node(c));
+  count_bytes(c, n);
+}
+template <bool kRoot> EMAT_NOTAIL EMAT_DN void branch_reform_move_picked(Ctx& c, int X) { EMAT_TIMED(2); ByteCount n; begin_move(c, k_branch_reform); branch_reform_body<kRoot>(c, n, X); count_bytes(c, n); }
 
 // subrun.cpp:325-350, iterative with an explicit stack in scratch
 EMAT_DN SVec<int> enumerate_descendant_branches_straddling(Ctx& c, int P, double t, int X) {
@@ -634,13 +639,129 @@ EMAT_DN bool make_heap_room(Ctx& c) {
   return true;
 }
 
+// Row `at` of the trace ring for a move settled in the frame, as mcmc_sub_iteration forms it from Ctx::tr_* (the caller has found
+// at < trace_cap): kind, node, verdict, log MH ratio; a move that was not noted (acc < 0) reads "not accepted, NaN".
+EMAT_DF void store_trace_row(Ctx& c, int at, int kind, int node, int acc, double log_mh) {
+  double* tr = (double*)slab_at(c, hdr_of(c)->off_trace) + 4 * at;
+  const bool noted = acc >= 0;
+  tr[0] = (double)kind; tr[1] = (double)node; tr[2] = noted ? (double)acc : 0.0; tr[3] = noted ? log_mh : __builtin_nan("");
+}
+
+// ---- moves that end at once, settled in the chain's frame (parts without the run's root) ------------------------------------------
+// Two in five of a chain's moves at C4 change nothing: a tip displacement of a tip whose date is exact (t_min == t_max: every tip of a
+// data set with exact dates), a branch reform that picks the part's root, and a branch reform of a branch without mutations, which
+// accepts g - g = 0 without a draw and adds 0 to log_G.  What such a move leaves is its draws gone from the stream, three or four
+// counters and, when tracing, a row.  settle_moves makes the draw that picks the move and the pick of the node itself -- the same words
+// of the stream through the same arithmetic (mix_draw, uniform_pick) -- and, while moves end at once, stays in one straight stretch
+// without a call: stream position, moves left and the counters' increments are held in registers and stored once when the run ends.
+// Per move it makes the chain's own tests (moves left, rng_pos_wants_fill), so a run ends exactly where the chain would have parked or
+// stopped.  It enters with one move's frame begun (run_chain has counted it, mcmc_sub_iteration has checked the heap mark and reset
+// the arena; a settled move touches neither, so both still hold for the move that ends the run) and says how it left:
+enum {
+  k_all_settled = 0,       // every move begun is settled; the chain's loop tests again before it begins the next
+  k_move_undrawn,          // one move is begun and nothing of it drawn (the next word lies beyond the words computed ahead)
+  k_move_drawn,            // ... its draw `r` is made, nothing else: every kind the stretch does not look into, and a pick that ran out of words
+  k_tip_picked,            // ... a tip displacement that is a real move, its tip `node` picked
+  k_reform_picked          // ... a branch reform that is a real move, its branch `node` picked
+};
+struct Unsettled {
+  int what; int node; double r;
+#ifdef EMAT_PROFILE_PHASES
+  long long t0;            // when the move that ends the run began
+#endif
+};
+// The longest run (1: every settled move stores its own counters and goes back to the chain's loop -- the A/B of the run against the pick alone).
+#ifndef EMAT_SETTLE_RUN_MAX
+#define EMAT_SETTLE_RUN_MAX 0x7fffffffu
+#endif
+// The draw that picks a move, of the word it takes: uniform_co(c, 0.0, mix_total) spelled on the word.
+EMAT_DF double mix_draw(uint64_t word, double mix_total) { return 0.0 + (mix_total - 0.0) * to_co(word); }
+EMAT_DF Unsettled settle_moves(Ctx& c) {
+  Unsettled u; u.what = k_all_settled; u.node = -1; u.r = 0.0;
+  const int n_nodes = (int)uniform_u32((uint32_t)hdr_of(c)->n_nodes), root = (int)uniform_u32((uint32_t)hdr_of(c)->root);
+  const int trace_cap = (int)uniform_u32((uint32_t)hdr_of(c)->trace_cap), trace_len = (int)uniform_u32((uint32_t)hdr_of(c)->trace_len);
+  const double mix_total = c.mix_total;
+  const int64_t left_at_entry = c.moves_left;
+  uint32_t pos = uniform_u32(c.rng_pos);
+  // moves settled so far, by what they count: exact tips (proposed[1]), reforms that picked the root (proposed[2]), reforms of a branch
+  // without mutations (proposed[2], accepted[2], 128 algorithmic bytes); rows written
+  uint32_t n_tip = 0, n_root = 0, n_empty = 0, n_rows = 0;
+  for (;;) {
+#ifdef EMAT_PROFILE_PHASES
+    u.t0 = clock64();
+#endif
+    if (!rng_pos_in_buffer(pos, k_rng_blocks)) { u.what = k_move_undrawn; break; }
+    const double r = mix_draw(rng_buffer_word(pos), mix_total);
+    pos += 1u;
+    int kind = -1, node = -1, acc = -1;
+    if (uniform_flag(r < 7.5)) { u.what = k_move_drawn; u.r = r; break; }
+    else if (uniform_flag(r < 15.0)) {
+      // tip_displace_move's pick loop (pick_random_tip) on the words computed ahead; should they run out, the pick is made again the general way
+      const uint32_t pos_at_pick = pos;
+      bool ran_out = false;
+      int guard = 0;
+      do {
+        if (!rng_pos_in_buffer(pos, k_rng_blocks)) { ran_out = true; break; }
+        node = (int)uniform_u32((uint32_t)uniform_pick(rng_buffer_word(pos), n_nodes));
+        pos += 1u;
+      } while (uniform_flag(!is_tip(c, node)) && guard++ < (1 << 26));
+      if (ran_out) { pos = pos_at_pick; u.what = k_move_drawn; u.r = r; break; }
+      if (!uniform_flag(nodes_of(c)[node].t_min == nodes_of(c)[node].t_max)) { u.what = k_tip_picked; u.node = node; break; }
+      kind = k_tip_displace; n_tip += 1u;
+    } else if (uniform_flag(r < 30.0)) {
+      if (n_nodes < 3 || !rng_pos_in_buffer(pos, k_rng_blocks)) { u.what = k_move_drawn; u.r = r; break; }
+      node = (int)uniform_u32((uint32_t)uniform_pick(rng_buffer_word(pos), n_nodes));
+      pos += 1u;
+      kind = k_branch_reform;
+      if (node == root) n_root += 1u;
+      else {
+        if (uniform_flag(nmuts(c, node) != 0)) { u.what = k_reform_picked; u.node = node; break; }
+        // branch_reform_body's n == 0 path, its arithmetic as it stands: g - g is 0, accepted without a draw -- unless g is not finite, and
+        // then the move, which draws, is made the general way
+        const int P = nodes_of(c)[node].parent;
+        const double t_X = nodes_of(c)[node].t, t_P = nodes_of(c)[P].t;
+        const double lam = nodes_of(c)[node].lambda;
+        const double g = -lam * (t_X - t_P), delta_log_G = g - g;
+        if (!uniform_flag(delta_log_G >= 0.0)) { u.what = k_reform_picked; u.node = node; break; }
+        acc = 1; n_empty += 1u;   // (delta_log_G is +0.0 here: what it adds to log_G is added once, below)
+      }
+    } else { u.what = k_move_drawn; u.r = r; break; }
+    // the move is settled
+    if (trace_len + (int)n_rows < trace_cap) { store_trace_row(c, trace_len + (int)n_rows, kind, node, acc, 0.0); n_rows += 1u; }
+#ifdef EMAT_PROFILE_PHASES
+    { const long long _dt = clock64() - u.t0; hdr_of(c)->phase_ticks[14] += _dt; if (kind == k_tip_displace) EMAT_COUNT(c, 15, _dt); }
+#endif
+    // the chain's tests before the next move, on the values held here (run_chain makes them again on what is stored below)
+    const uint32_t n_settled = n_tip + n_root + n_empty;
+    const int64_t left = left_at_entry - (int64_t)(n_settled - 1u);   // c.moves_left as the chain would hold it now: the frame begun at entry is the first settled
+    if (uniform_flag(left <= 0) || n_settled == EMAT_SETTLE_RUN_MAX) break;    // (the second: the counts are 32-bit; the chain simply begins another run)
+    if (rng_pos_wants_fill(pos, k_rng_blocks, (uint32_t)EMAT_RNG_MARGIN)) break;
+  }
+  // A run that ends with a move begun has counted that move's frame too.
+  const uint32_t n_settled = n_tip + n_root + n_empty, n_begun = n_settled + (u.what == k_all_settled ? 0u : 1u);
+  c.rng_pos = pos;
+  if (n_settled != 0u) {
+    c.moves_left = left_at_entry - (int64_t)(n_begun - 1u);
+    hdr_of(c)->proposed[k_tip_displace] += (int64_t)n_tip;
+    hdr_of(c)->proposed[k_branch_reform] += (int64_t)(n_root + n_empty);
+    hdr_of(c)->accepted[k_branch_reform] += (int64_t)n_empty;
+    hdr_of(c)->moves_done += (int64_t)n_settled;
+    c.bytes += (int64_t)(2u * 64u * n_empty);
+    // log_G += 0.0 once for all of them: x + 0.0 is x for every x but -0.0, which the first addition turns into +0.0 and the later ones leave
+    if (n_empty != 0u) hdr_of(c)->log_G += 0.0;
+    if (n_rows != 0u) hdr_of(c)->trace_len = trace_len + (int)n_rows;
+  }
+  return u;
+}
+
 // Subrun::mcmc_sub_iteration (subrun.cpp:98-121).  Returns false when the part must stop.  An SPR1 move parks itself
 // twice for the wave's scan + study (c.svc != 0 on return): the next call resumes it.
 // kRoot: the part holds the run's root (Ctx::includes_run_root, fixed for the part's life).  Only that part can stop a move to have its
-// grid regrown and rewind its random stream to the move's first draw (stop_for_cells), so only it remembers where that was.
+// grid regrown and rewind its random stream to the move's first draw (stop_for_cells), so only it remembers where that was.  Every
+// other part settles the moves that end at once here, in the frame (settle_moves), and calls a move only when it is a real one.
 template <bool kRoot> EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
 #ifdef EMAT_PROFILE_PHASES
-  const long long _mv0 = clock64();
+  long long _mv0 = clock64();
 #endif
   // (what the frame branches on is said to be uniform where it is loaded or returned: uniform_flag, emat_device_core.hpp)
   const uint32_t phase = uniform_u32(c.phase);
@@ -652,7 +773,25 @@ template <bool kRoot> EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
   sc_reset(c);
   if (kRoot) c.mv_rng_pos = c.rng_pos;
   if (c.only_displacing_inner_nodes) inner_node_displace_move<kRoot>(c);
-  else {
+  else if (!kRoot) {
+    const Unsettled u = settle_moves(c);
+    const int what = (int)uniform_u32((uint32_t)u.what);
+    if (what == k_all_settled) return true;
+#ifdef EMAT_PROFILE_PHASES
+    _mv0 = u.t0;
+#endif
+    if (what == k_tip_picked) tip_displace_move_picked<kRoot>(c, u.node);
+    else if (what == k_reform_picked) branch_reform_move_picked<kRoot>(c, u.node);
+    else {
+      // the general way: the draws settle_moves did not make are made here, through rng_next64
+      const double r = what == k_move_drawn ? u.r : uniform_co(c, 0.0, c.mix_total);
+      if (r < 7.5) inner_node_displace_move<kRoot>(c);
+      else if (r < 15.0) tip_displace_move_picked<kRoot>(c, pick_random_tip(c));
+      else if (r < 30.0) { if (hdr_of(c)->n_nodes < 3) begin_move(c, k_branch_reform); else branch_reform_move_picked<kRoot>(c, pick_random_node(c)); }
+      else if (c.topology_moves_enabled) { if (r < 31.0) subtree_slide_move(c); else spr1_move_begin(c); }
+      else trace_nothing(c, -1);
+    }
+  } else {
     double r = uniform_co(c, 0.0, c.mix_total);
     if (r < 7.5) inner_node_displace_move<kRoot>(c);
     else if (r < 15.0) tip_displace_move<kRoot>(c);
@@ -682,6 +821,8 @@ template <bool kRoot> EMAT_NOTAIL EMAT_D bool mcmc_sub_iteration(Ctx& c) {
 // whatever their caller kept in registers would be spilled and reloaded around each of them.
 // Returns with c.svc != 0 when the current move waits for the wave (the kernel serves it and calls again), else when the
 // moves are done or the part had to stop.
+// In a part without the run's root, one turn of the loop may settle a whole run of moves that end at once (settle_moves, which counts
+// them off c.moves_left itself); the tests at the top of the loop are then made again on what it stored.
 template <bool kRoot> EMAT_NOTAIL EMAT_DN void run_chain(Ctx& c) {
   c.svc = 0;
   for (;;) {
