@@ -11,7 +11,15 @@ to the identities the move code implies (emat_device_moves.hpp; the reference's 
   missing intervals (exact_model.displacement_slope), as Fractions;
 - the displacement of the run's root is a symmetric step: log_mh = delta log G + delta partial prior;
 - a branch reform re-times one branch's mutations uniformly: log_mh = delta log G, the prior and k_bar_p untouched;
+- an accepted subtree slide of X (spr_move_core, subrun.cpp:683-742; the slide's own Hastings factor, subrun.cpp:352-448): log_mh =
+  [delta_log_G - log_alpha_mut](the model's graft of X on the tree after) - [the same on the tree before] + log(alpha_ratio) +
+  partial prior(after) - partial prior(before).  The grafts are tests/graft_model.py's, at mu_proposal = lambda(root) / (L - sites
+  missing at the root) of the tree BEFORE, taken exactly (its own bound, times log_alpha_mut's sensitivity to mu, joins the bound).  alpha_ratio from the tree before, X and
+  the new time: 1 along the same branch; 1/n up past an ancestor, n the branches that straddle the OLD time below the new sibling
+  with X's subtree pruned; n down past the sibling, n the branches that straddle the NEW time below P with X's subtree pruned.  The new
+  graft's history is read from the tree after, so this also says that log_alpha_mut is the density of the history written;
 - for all five kinds the increment of the maintained log_G and log_aug_prior over the one move is the exact difference.
+SPR1 stays outside: its log_mh adds log_alpha_n2o - log_alpha_o2n from the candidate study (region weights and time density).
 
 Bounds.  A log_mh or an increment is held to the `Exact.bound()` of the difference, whose S holds only the terms that differ
 (exact_model's docstring).  Added to it, each named:
@@ -19,7 +27,11 @@ Bounds.  A log_mh or an increment is held to the `Exact.bound()` of the differen
   same number) gets the sum over the cells that differ of |w (k A - c)| times check_part's k_bar_p allowance at that move count;
 - the increment of a total gets 2 u max(|total before|, |total after|): the one addition at the total's magnitude;
 - a simple displacement's log_mh adds delta log G and takes the proposal ratio, the same product, away again: twice that
-  product's magnitude joins S (exact_model's docstring, last rule).
+  product's magnitude joins S (exact_model's docstring, last rule);
+- an accepted slide's log_mh gets the sum of its four graft numbers' own Exact.bound() (each formed whole), the prior difference's
+  with its k_bar_p allowance, 8 u |log alpha_ratio|, and for the computed proposal rate (n_lambda + 9) u S_mu times the sum over both
+  log_alpha_mut's terms of |d term / d mu| (the rate's error reaches log_mh only through that derivative, so the rate's term count
+  does not multiply the whole of log_alpha_mut's S).
 
 One row, two decisions.  In the part that holds the run's root, a branch reform of a child of the root first runs
 spr_move_core in place (subrun.cpp:298-303: the mutations of both root branches "dance"), which accepts or rejects on its own
@@ -45,6 +57,7 @@ from fractions import Fraction as F
 import numpy as np
 
 import exact_model as X
+import graft_model as GM
 
 KINDS = ("inner_node_displace", "tip_displace", "branch_reform", "subtree_slide", "spr1")
 _TOPO = ("root", "parent", "child0", "child1", "t_min", "t_max", "mut_offset", "miss_offset", "miss_start", "miss_end", "mfs_offset", "mfs_site", "mfs_state")
@@ -194,7 +207,9 @@ class Coverage:
     """What the checked steps of a test file amount to (the conditions of the issue are asserted on the sum over its cases)."""
     FIELDS = ("steps", "accepted", "accepted_root_displacements", "accepted_negative_log_mh", "accepted_while_grid_grew",
               "accepted_reform_same_site_twice", "accepted_reform_more_than_32", "accepted_outside_root_part", "compound", "compound_accepted",
-              "rejected_topology", "rejected_rooty_not_bit_identical", "rejected_topology_lambda_not_bit_identical", "unchecked")
+              "rejected_topology", "rejected_rooty_not_bit_identical", "rejected_topology_lambda_not_bit_identical", "unchecked",
+              "accepted_slides_log_mh_exact", "accepted_slide_kinds")
+    SLIDE_KINDS = ("same branch", "up with n >= 2", "down with n >= 2", "X under the run's root", "X in a part without the run's root")
 
     def __init__(self):
         self.steps = 0
@@ -203,6 +218,8 @@ class Coverage:
         self.accepted_root_displacements = self.accepted_while_grid_grew = self.accepted_reform_same_site_twice = 0
         self.accepted_reform_more_than_32 = self.accepted_outside_root_part = self.compound = self.compound_accepted = 0
         self.rejected_topology = self.rejected_rooty_not_bit_identical = self.rejected_topology_lambda_not_bit_identical = self.unchecked = 0
+        self.accepted_slides_log_mh_exact = 0
+        self.accepted_slide_kinds = [0] * len(self.SLIDE_KINDS)       # accepted slides held to the identity, per SLIDE_KINDS
 
     def add(self, o):
         for f in self.FIELDS:
@@ -222,6 +239,8 @@ class Coverage:
         assert self.accepted_reform_same_site_twice >= 1, d
         assert self.accepted_reform_more_than_32 >= 1, d
         assert self.accepted_outside_root_part >= 100, d
+        assert self.accepted_slides_log_mh_exact == self.accepted[3], d      # every accepted slide was held to the identity
+        assert self.accepted_slides_log_mh_exact >= 1 and min(self.accepted_slide_kinds) >= 1, (dict(zip(self.SLIDE_KINDS, self.accepted_slide_kinds)), d)
 
 
 class PartWatch:
@@ -422,7 +441,10 @@ def check_step(tally, cov, w: PartWatch, step, b, a):
             tally.check("log_mh_branch_reform", dG, log_mh, where)
             if dP.cells or dP.value != 0 or _bits(a["A"]) != _bits(b["A"]) or _bits(taba["k_bar_p"]) != _bits(tabb["k_bar_p"]):
                 fails.append("%s: a branch reform touched the prior or k_bar_p" % where)
-        # (subtree slide, SPR1: the proposal-density part of log_mh is out of scope; their increments are checked above)
+        elif kind == 3 and acc:
+            check_accepted_slide(tally, cov, w, node, dvA, dP, k_term, log_mh, where)
+        # (a slide that was not accepted leaves no second state to read its proposed history from; SPR1's log_mh adds the candidate
+        # study's log_alpha_n2o - log_alpha_o2n, which is outside this file: the increments of both are checked above)
 
         if acc:
             cov.accepted[kind] += 1
@@ -436,6 +458,69 @@ def check_step(tally, cov, w: PartWatch, step, b, a):
     except AssertionError as e:
         fails.append("%s: %s" % (where, e))
         cov.unchecked += 1
+
+
+def slide_alpha_ratio(B, A, Xn):
+    """(alpha_ratio, kind, n) of the subtree slide that took tree B to tree A (exact_model._Tree) by moving X: from the tree before,
+    X and the new time of X's parent.  kind: "same", "up" or "down"; n: the branches the slide chose among on its way back (up) or
+    there (down)."""
+    P = B.parent[Xn]
+    assert P >= 0 and A.parent[Xn] == P, "X's parent is another node"
+    S = [k for k in B.kids[P] if k != Xn][0]
+    SS = [k for k in A.kids[P] if k != Xn][0]
+    old_t, new_t = B.t[P], A.t[P]
+
+    def straddling(top, t):         # branches below `top` that hold time t, X's subtree pruned
+        out, st = [], [top]
+        while st:
+            v = st.pop()
+            if v == Xn:
+                continue
+            if t <= B.t[v]:
+                out.append(v)
+            else:
+                st += B.kids[v]
+        return out
+    if SS == S:
+        G = B.parent[P]
+        assert new_t < min(B.t[Xn], B.t[S]) and (G < 0 or B.t[G] <= new_t), "the new time is not on the branch above X's sibling"
+        return F(1), "same", 1
+    anc, v = [], B.parent[P]
+    while v >= 0:
+        anc.append(v); v = B.parent[v]
+    if SS in anc:
+        G = B.parent[SS]
+        assert new_t < B.t[SS] and (G < 0 or B.t[G] <= new_t), "the new time is not on the branch above the ancestor"
+        n = len(straddling(SS, old_t))
+        assert P in straddling(SS, old_t)
+        return F(1, n), "up", n
+    br = straddling(P, new_t)
+    assert SS in br and new_t > B.t[S], "the new sibling does not straddle the new time below P"
+    return F(len(br)), "down", len(br)
+
+
+def check_accepted_slide(tally, cov, w, Xn, dvA, dP, k_term, log_mh, where):
+    """The identity of an accepted subtree slide (the module's docstring)."""
+    B, A = w.dv.T, dvA.T
+    ratio, kind, n = slide_alpha_ratio(B, A, Xn)
+    lam = w.dv.lambda_i(B.root)
+    sites = len(w.ref) - w.dv.nsm[B.root]
+    mu, mu_S, mu_n = lam.value / sites, lam.S / sites, lam.n + 1
+    gb = GM.GraftModel(w.dv, w.ref, w.ev, w.includes_root).graft(Xn)
+    ga = GM.GraftModel(dvA, w.ref, w.ev, w.includes_root).graft(Xn)
+    terms = [ga.delta_log_G, ga.log_alpha_mut(mu), gb.delta_log_G, gb.log_alpha_mut(mu)]
+    # mu is itself computed: its own bound (mu_n + 8) u mu_S, times what an error of mu moves the two log_alpha_mut by
+    mu_term = (mu_n + 8) * X.U * float(mu_S * (ga.mu_sensitivity(mu) + gb.mu_sensitivity(mu)))
+    lr = X._log(ratio)
+    v = (terms[0].value - terms[1].value) - (terms[2].value - terms[3].value) + lr + dP.value
+    S = sum((t.S for t in terms), dP.S + abs(lr))
+    bound = sum(t.bound() for t in terms) + mu_term + dP.bound() + k_term + 8 * X.U * abs(float(lr))
+    ex = X.Exact(v, S, 0)
+    tally.check("log_mh_subtree_slide", ex, log_mh, "%s [%s, n %d]" % (where, kind, n), bound - ex.bound())
+    cov.accepted_slides_log_mh_exact += 1
+    rooty = w.includes_root and (B.parent[Xn] == B.root or A.parent[Xn] == A.root)
+    for i, hit in enumerate((kind == "same", kind == "up" and n >= 2, kind == "down" and n >= 2, rooty, not w.includes_root)):
+        cov.accepted_slide_kinds[i] += int(hit)
 
 
 def run_stepped(tally, cov, engine, sc, parts, incl, ref, ev, pop, steps, tag="", watch=None, advance=advance_one_move):

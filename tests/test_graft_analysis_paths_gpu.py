@@ -27,15 +27,16 @@ SPINE_TIPS = 24
 MU_PROPOSAL = 1e-3
 # Minimum counts over the analysed grafts of ONE cut, from the oracle's results (never the device's)
 REQUIRED = {"levels_above_PX >= 2": 20, "branch_infos > 4": 5, "hot mutations": 20, "hot mutations of two levels": 5, "S misses nothing": 10}
-REQUIRED_ROOT_PART = {"ends in the open branch": 3}
+REQUIRED_ROOT_PART = {"ends in the open branch": 3, "rooty grafts": 2}
 REQUIRED_CUT = {"ends at a non-root part's root": 5}
 
 
-def _gapped_third(tree, td, sites):
+def _gapped_third(tree, td, sites, spine_tips=SPINE_TIPS, every_tip=False):
     """Tip descriptors with missing stretches at a third of the tips and none at the others.  The third: the tips of the small clades that hang
     off the spine from the root towards the larger clade -- they also share one stretch, so that the analysis of a spine node still slides
     missing sites when it reaches the root -- and then runs of neighbours in leaf order, each with a tip or two that miss nothing in between,
-    so that a graft's sibling and the siblings above it miss overlapping sites.  A tip's deltas inside its missing sites are dropped."""
+    so that a graft's sibling and the siblings above it miss overlapping sites.  A tip's deltas inside its missing sites are dropped.
+    `every_tip`: the generator's gaps kept at every tip instead (no spine, no shared stretch): both children of the root then miss sites."""
     n = td.num_tips
     size = np.ones(tree.num_nodes, np.int64)
     order, pre, stack = [], [], [int(tree.root)]
@@ -63,10 +64,12 @@ def _gapped_third(tree, td, sites):
     while tree.child0[v] >= 0:
         a, b = int(tree.child0[v]), int(tree.child1[v])
         small, big = (a, b) if size[a] <= size[b] else (b, a)
-        if len(spine) + size[small] > SPINE_TIPS:
+        if len(spine) + size[small] > spine_tips:
             break
         spine += leaves(small); v = big
-    keep = np.zeros(n, bool); keep[spine] = True
+    if every_tip:
+        spine = []
+    keep = np.full(n, bool(every_tip)); keep[spine] = True
     for pos, t in enumerate(order):
         if keep.sum() >= n // 3:
             break
@@ -99,30 +102,33 @@ def _gapped_third(tree, td, sites):
 
 
 @functools.lru_cache(maxsize=None)
-def scenario():
+def scenario(tips_n=TIPS, sites=SITES, seed=SEED, spine_tips=SPINE_TIPS, every_tip=False):
     """C1-sized, 300 sites, six short gaps per gapped tip: the synthetic tips, gaps kept at a third of them, and the product's default builder's
-    tree for those tips (host code) -- so every list of the tree is what the product itself makes of such data."""
-    p = d.SynthParams(num_tips=TIPS, num_sites=SITES, tip_span=365.0, pop_n0=365.0, pop_growth=0.0, mu=MU_SCALE * 1e-3 / 365.0, gaps_per_tip=6, mean_gap_len=25.0, seed=SEED)
+    tree for those tips (host code) -- so every list of the tree is what the product itself makes of such data.  (Other sizes from the same
+    generator with the same gap rule, and `every_tip` gapped: tests/test_graft_model.py's further scenarios.)"""
+    p = d.SynthParams(num_tips=tips_n, num_sites=sites, tip_span=365.0, pop_n0=365.0, pop_growth=0.0, mu=MU_SCALE * 1e-3 / 365.0, gaps_per_tip=6, mean_gap_len=25.0, seed=seed)
     p.pi, p.kappa = PI, KAPPA
     tree, ref, tmax = d.make_synthetic_emat(p)
     ob = OracleBuild(ref)
     try:
-        tips, gapped = _gapped_third(tree, ob.tip_descs_of(tree), SITES)
+        tips, gapped = _gapped_third(tree, ob.tip_descs_of(tree), sites, spine_tips, every_tip)
     finally:
         ob.close()
-    assert gapped == TIPS // 3
-    b = d.EmatBackend(SITES, device=-1)
+    assert gapped == (tips_n if every_tip else tips_n // 3)
+    b = d.EmatBackend(sites, device=-1)
     try:
         b.set_ref_sequence(ref)
-        built, built_ref, _ = b.build_default(tips, SEED)
+        built, built_ref, _ = b.build_default(tips, seed)
     finally:
         b.close()
-    return Scenario("graft-paths", built, built_ref, tmax, p.mu, KAPPA, PI, d.PopModel.exp(tmax, 365.0, 0.0, 0.0), SITES)
+    return Scenario("graft-paths", built, built_ref, tmax, p.mu, KAPPA, PI, d.PopModel.exp(tmax, 365.0, 0.0, 0.0), sites)
 
 
 @functools.lru_cache(maxsize=None)
 def reference(num_parts):
-    """(the cut, {(part, X): the oracle's analysis}) of every inner X whose parent is not the part's root; computed once, never changed."""
+    """(the cut, {(part, X): the oracle's analysis}) of every X the move code can analyse: every node but the part's root and, in a part that
+    does not hold the run's root, the root's children (spr_move_core returns before the analysis there); the children of the run's root in the
+    root part are the rooty grafts.  Computed once, never changed."""
     sc = scenario()
     cut = split_parts(sc, num_parts, 11)
     parts, incl, seeds, root_part, ref = cut
@@ -132,7 +138,7 @@ def reference(num_parts):
         want = {}
         for p, t in enumerate(parts):
             for X in range(t.num_nodes):
-                if X != t.root and int(t.parent[X]) != t.root:
+                if X != t.root and (incl[p] or int(t.parent[X]) != t.root):
                     want[(p, X)] = orc.debug_graft(p, X, MU_PROPOSAL)["grafts"][0]
     finally:
         orc.close()
@@ -144,6 +150,9 @@ def coverage(num_parts):
     c = dict.fromkeys(list(REQUIRED) + list(REQUIRED_ROOT_PART) + list(REQUIRED_CUT), 0)
     for (p, X), g in want.items():
         bis, t = g["branch_infos"], parts[p]
+        if int(t.parent[X]) == t.root:          # a rooty graft: P -> X and P -> S open, S -> P -> X closed; the counts below are the inner grafts'
+            c["rooty grafts"] += len(bis) == 3 and [b["is_open"] for b in bis] == [True, True, False]
+            continue
         c["levels_above_PX >= 2"] += sum(1 for b in bis[1:] if not b["is_open"]) >= 2
         c["branch_infos > 4"] += len(bis) > 4
         c["ends in the open branch"] += bis[-1]["is_open"]

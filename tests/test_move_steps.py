@@ -2,6 +2,11 @@
 bounds).  The oracle is the engine under test here, so the identities are proved without a GPU; test_move_steps_gpu.py points
 the same cases at the device.
 
+An accepted subtree slide's whole log_mh is one of the identities (move_steps.check_accepted_slide: the four graft numbers of
+tests/graft_model.py, the slide's Hastings factor and the exact prior difference).  Over CASES the oracle accepts 60 slides: 54
+along the same branch, 4 up past an ancestor and 2 down past the sibling with two or more branches to choose from, 4 of a child
+of the run's root, 25 in parts without the run's root; Coverage.assert_conditions requires at least one of each kind.
+
 What a rejected topology move gives back, as this file establishes on the oracle (check_step asserts it of every rejected
 subtree slide and SPR1 move of these cases; Coverage counts them): mutation times BIT FOR BIT, except on the sibling branch of a
 subtree pruned from under the run's root (reflected about the root's time and back: held to four roundings); lambda_i bit for
