@@ -422,6 +422,12 @@ int orc_part_get_stats(orc_engine* e, int part_id, emat_part_stats* out) {
   out->rng_draws = (int64_t)pt.rng.counter;
   return EMAT_OK;
 }
+// Where the part's Philox stream stands, as the engine's emat_part_get_rng reports it: key, blocks opened, pending half block.
+int orc_part_rng(orc_engine* e, int part_id, uint64_t* key, uint64_t* counter, uint64_t* spare, int32_t* has_spare) {
+  auto& r = e->parts.at(part_id)->rng;
+  *key = r.key; *counter = r.counter; *spare = r.spare; *has_spare = r.has_spare ? 1 : 0;
+  return EMAT_OK;
+}
 int orc_part_get_trace(orc_engine* e, int part_id, int* num_moves, double* trace) {
   auto& tr = e->parts.at(part_id)->subrun->trace;
   int n = std::min<int>(*num_moves, (int)tr.size());

@@ -32,6 +32,7 @@ def configure(engine, sc, ref, parts, incl, seeds, root_part, t_step=None, topol
         engine.set_hky(sc.mu, sc.kappa, sc.pi, nu_l)
     engine.set_flags(sc.t_max_tip, only_displace, topology)
     engine.upload_parts(parts, incl, seeds)
+    engine._part_seeds = [int(x) for x in seeds]       # (a part's seed is its random stream's key: move_steps.stream_position)
     engine.build_coalescent_parts(sc.pop, root_part, t_step if t_step is not None else sc.default_t_step())
 
 

@@ -19,7 +19,14 @@ to the identities the move code implies (emat_device_moves.hpp; the reference's 
   with X's subtree pruned; n down past the sibling, n the branches that straddle the NEW time below P with X's subtree pruned.  The new
   graft's history is read from the tree after, so this also says that log_alpha_mut is the density of the history written;
 - for all five kinds the increment of the maintained log_G and log_aug_prior over the one move is the exact difference.
-SPR1 stays outside: its log_mh adds log_alpha_n2o - log_alpha_o2n from the candidate study (region weights and time density).
+- an accepted SPR1 move of X (subrun.cpp:492-675): log_mh = [delta_log_G - log_alpha_mut](new graft) - [the same](old graft) +
+  log_alpha_n2o - log_alpha_o2n + partial prior(after) - partial prior(before).  The graft terms are the slide's; log_alpha_o2n is the
+  density of (new sibling's region, new t_P) in the study of tests/study_model.py scanned from the old sibling, log_alpha_n2o that of
+  (old sibling, old t_P) in the study scanned from the new one, both on the tree with X's graft read off (asserted to be the same tree
+  before and after), at the scan limit the move's second draw gave.  The limit is read from the part's random stream before the move:
+  its first word through mix_draw must say SPR1 (asserted), its second through to_co is below 0.01 for an unlimited scan.  The model is
+  evaluated at that limit only.  What the move DREW (the region and the time in it) is not held to anything here: the pick depends on
+  the depth-first order, which only the algorithm defines;
 
 Bounds.  A log_mh or an increment is held to the `Exact.bound()` of the difference, whose S holds only the terms that differ
 (exact_model's docstring).  Added to it, each named:
@@ -31,7 +38,10 @@ Bounds.  A log_mh or an increment is held to the `Exact.bound()` of the differen
 - an accepted slide's log_mh gets the sum of its four graft numbers' own Exact.bound() (each formed whole), the prior difference's
   with its k_bar_p allowance, 8 u |log alpha_ratio|, and for the computed proposal rate (n_lambda + 9) u S_mu times the sum over both
   log_alpha_mut's terms of |d term / d mu| (the rate's error reaches log_mh only through that derivative, so the rate's term count
-  does not multiply the whole of log_alpha_mut's S).
+  does not multiply the whole of log_alpha_mut's S);
+- an accepted SPR1's log_mh gets the same four graft bounds, the rate's term and the prior's with k_bar_p's allowance, the two densities'
+  own Exact.bound(), their gamma_term where a region above the root is involved, and for the computed lambda_X
+  (n_lambda + 8) u S_lambda / lambda_X times the two densities' lambda_sensitivity (study_model's docstring names each).
 
 One row, two decisions.  In the part that holds the run's root, a branch reform of a child of the root first runs
 spr_move_core in place (subrun.cpp:298-303: the mutations of both root branches "dance"), which accepts or rejects on its own
@@ -58,6 +68,8 @@ import numpy as np
 
 import exact_model as X
 import graft_model as GM
+import skygrid_streams as RS
+import study_model as SM
 
 KINDS = ("inner_node_displace", "tip_displace", "branch_reform", "subtree_slide", "spr1")
 _TOPO = ("root", "parent", "child0", "child1", "t_min", "t_max", "mut_offset", "miss_offset", "miss_start", "miss_end", "mfs_offset", "mfs_site", "mfs_state")
@@ -71,8 +83,28 @@ def snapshot(engine, p):
     tree = engine.part_download(p)
     lam, nsm, G, A = engine.part_derived(p, tree.num_nodes)
     tr = engine.part_trace(p, max(int(st["moves_done"]), 1))
-    return dict(tree=tree, lam=lam, nsm=nsm, G=float(G), A=float(A), tab=engine.part_coalescent(p), stats=st,
+    return dict(tree=tree, lam=lam, nsm=nsm, G=float(G), A=float(A), tab=engine.part_coalescent(p), stats=st, rng=stream_position(engine, p, st),
                 row=tr[-1].copy() if tr.shape[0] else None, trace_len=tr.shape[0])
+
+
+def stream_position(engine, p, stats=None):
+    """Where part p's random stream stands: engine.part_rng(p).  The device reports it only while the parts lie on it -- not before the
+    first pass, nor between a pass that stopped for room and the next.  Then the position is put together from what the host keeps: the
+    key (the part's seed, helpers.configure notes it; or the key read earlier) and the blocks opened (part_stats), with has_spare = None:
+    whether half a block is pending is not known, unless no block has been opened."""
+    keys = engine.__dict__.setdefault("_stream_keys", {})
+    try:
+        r = engine.part_rng(p)
+        keys[p] = r["key"]
+        return r
+    except Exception as e:
+        if "not on a device" not in str(e):
+            raise
+    key = keys.get(p)
+    if key is None:
+        key = int(getattr(engine, "_part_seeds")[p])
+    ctr = int((stats or engine.part_stats(p))["rng_draws"])
+    return dict(key=key, counter=ctr, spare=None, has_spare=False if ctr == 0 else None)
 
 
 def advance_one_move(engine):
@@ -208,8 +240,11 @@ class Coverage:
     FIELDS = ("steps", "accepted", "accepted_root_displacements", "accepted_negative_log_mh", "accepted_while_grid_grew",
               "accepted_reform_same_site_twice", "accepted_reform_more_than_32", "accepted_outside_root_part", "compound", "compound_accepted",
               "rejected_topology", "rejected_rooty_not_bit_identical", "rejected_topology_lambda_not_bit_identical", "unchecked",
-              "accepted_slides_log_mh_exact", "accepted_slide_kinds")
+              "accepted_slides_log_mh_exact", "accepted_slide_kinds", "accepted_spr1_log_mh_exact", "accepted_spr1_classes")
     SLIDE_KINDS = ("same branch", "up with n >= 2", "down with n >= 2", "X under the run's root", "X in a part without the run's root")
+    SPR1_CLASSES = ("unlimited scan", "new region above the root, gamma", "new region above the root, power law", "old region above the root",
+                    "part without the run's root", "min_muts >= 1 in the new region", "uncounted mutation on the path", "more than 64 regions",
+                    "more than 640 regions")
 
     def __init__(self):
         self.steps = 0
@@ -220,6 +255,8 @@ class Coverage:
         self.rejected_topology = self.rejected_rooty_not_bit_identical = self.rejected_topology_lambda_not_bit_identical = self.unchecked = 0
         self.accepted_slides_log_mh_exact = 0
         self.accepted_slide_kinds = [0] * len(self.SLIDE_KINDS)       # accepted slides held to the identity, per SLIDE_KINDS
+        self.accepted_spr1_log_mh_exact = 0
+        self.accepted_spr1_classes = [0] * len(self.SPR1_CLASSES)     # accepted SPR1 moves held to the identity, per SPR1_CLASSES
 
     def add(self, o):
         for f in self.FIELDS:
@@ -241,6 +278,7 @@ class Coverage:
         assert self.accepted_outside_root_part >= 100, d
         assert self.accepted_slides_log_mh_exact == self.accepted[3], d      # every accepted slide was held to the identity
         assert self.accepted_slides_log_mh_exact >= 1 and min(self.accepted_slide_kinds) >= 1, (dict(zip(self.SLIDE_KINDS, self.accepted_slide_kinds)), d)
+        assert self.accepted_spr1_log_mh_exact == self.accepted[4], d        # every accepted SPR1 move was held to the identity
 
 
 class PartWatch:
@@ -254,6 +292,7 @@ class PartWatch:
         self.kb = X.k_bar_p(self.dv.T, self.includes_root, tab["t_ref"], tab["t_step"], len(tab["k_bar_p"]))[0]
         self.kbf = np.array([abs(float(k)) for k in self.kb])      # |k_bar_p| as floats, for the allowance's kmax
         self.moves = 0          # since k_bar_p was built from scratch
+        self.t_max_tip = None   # the run's latest tip time (the studies above the root need it); run_stepped sets it
         assert_valid_part(first["tree"], ref)
 
     def k_allowance(self, tab):
@@ -443,8 +482,9 @@ def check_step(tally, cov, w: PartWatch, step, b, a):
                 fails.append("%s: a branch reform touched the prior or k_bar_p" % where)
         elif kind == 3 and acc:
             check_accepted_slide(tally, cov, w, node, dvA, dP, k_term, log_mh, where)
-        # (a slide that was not accepted leaves no second state to read its proposed history from; SPR1's log_mh adds the candidate
-        # study's log_alpha_n2o - log_alpha_o2n, which is outside this file: the increments of both are checked above)
+        elif kind == 4 and acc:
+            check_accepted_spr1(tally, cov, w, node, dvA, dP, k_term, log_mh, b["rng"], where)
+        # (a topology move that was not accepted leaves no second state to read its proposed history from: the increments are checked above)
 
         if acc:
             cov.accepted[kind] += 1
@@ -523,6 +563,98 @@ def check_accepted_slide(tally, cov, w, Xn, dvA, dP, k_term, log_mh, where):
         cov.accepted_slide_kinds[i] += int(hit)
 
 
+def scan_limit_from_stream(rng, mix_total=32.0):
+    """The scan limit of the SPR1 move that starts at stream position `rng` (a part_rng() dict read BEFORE the move): None for an unlimited
+    scan, 1 otherwise.  The move's first word through mix_draw (emat_device_moves.hpp: 0.0 + (mix_total - 0.0) * to_co(word)) must say SPR1,
+    r >= 31 of 32 with topology moves on; its second through to_co is the chooser (subrun.cpp:497-498: < 0.01 scans without a limit)."""
+    if rng["has_spare"] is None:            # (stream_position could not say: the two readings must agree, and one of them must say SPR1)
+        out = set()
+        for hs in (False, True):
+            try:
+                out.add(scan_limit_from_stream(dict(rng, has_spare=hs, spare=None), mix_total))
+            except AssertionError:
+                pass
+        assert len(out) == 1, "the stream's position is known to a half block only, and the two readings give %s" % sorted(map(str, out))
+        return out.pop()
+    key, ctr = np.uint64(rng["key"]), int(rng["counter"])
+    if rng["has_spare"]:                    # the second half of the block opened last is the next word
+        blk = RS.philox4x32_10(np.uint64(ctr - 1), key)
+        w1 = int(blk[2]) | (int(blk[3]) << 32)
+        assert rng["spare"] is None or w1 == int(rng["spare"]), "the stream's pending half block is not the second half of block %d" % (ctr - 1)
+        blk = RS.philox4x32_10(np.uint64(ctr), key)
+        w2 = int(blk[0]) | (int(blk[1]) << 32)
+    else:
+        blk = RS.philox4x32_10(np.uint64(ctr), key)
+        w1, w2 = int(blk[0]) | (int(blk[1]) << 32), int(blk[2]) | (int(blk[3]) << 32)
+    r = 0.0 + (mix_total - 0.0) * float(RS.to_co(np.uint64(w1)))
+    assert r >= mix_total - 1.0, "the move's first draw %r does not pick SPR1" % r
+    chooser = float(RS.to_co(np.uint64(w2)))
+    return None if chooser < 0.01 else 1
+
+
+def spr1_identity(w, Xn, dvA, limit):
+    """The pieces of an accepted SPR1's identity from the trees before (w.dv) and after (dvA): dict(grafts, mu, mu_term, o2n, n2o, lam,
+    pre, post, new_region, old_region)."""
+    B, A = w.dv.T, dvA.T
+    lam = w.dv.lambda_i(B.root)
+    sites = len(w.ref) - w.dv.nsm[B.root]
+    mu, mu_S, mu_n = lam.value / sites, lam.S / sites, lam.n + 1
+    gmb, gma = GM.GraftModel(w.dv, w.ref, w.ev, w.includes_root), GM.GraftModel(dvA, w.ref, w.ev, w.includes_root)
+    gb, ga = gmb.graft(Xn), gma.graft(Xn)
+    prb, pra = SM.Pruned(gmb, Xn), SM.Pruned(gma, Xn)
+    prb.same_as(pra)
+    lamX = w.dv.lambda_i(Xn)
+    assert lamX.value == dvA.lambda_i(Xn).value, "lambda of X changed"
+    pre = SM.Study(prb, w.includes_root, limit, lamX, w.t_max_tip)          # scanned from the old sibling
+    post = SM.Study(pra, w.includes_root, limit, lamX, w.t_max_tip)         # scanned from the new sibling
+    new_region = pre.find(ga.S, ga.t_P)
+    old_region = post.find(gb.S, gb.t_P)
+    assert new_region >= 0, "the new nexus (sibling %d, t_P %r) lies in no region of the study scanned from the old sibling" % (ga.S, ga.t_P)
+    assert old_region >= 0, "the old nexus (sibling %d, t_P %r) lies in no region of the study scanned from the new sibling" % (gb.S, gb.t_P)
+    o2n, n2o = pre.log_alpha(new_region, ga.t_P), post.log_alpha(old_region, gb.t_P)
+    # emat_device_moves.hpp:555-556, restated
+    assert pre.regions[new_region].m == sum(bi.d for bi in ga.infos if not bi.is_open), "min_muts of the new region is not the new graft's"
+    assert post.regions[old_region].m == sum(bi.d for bi in gb.infos if not bi.is_open), "min_muts of the old region is not the old graft's"
+    mu_term = (mu_n + 8) * X.U * float(mu_S * (ga.mu_sensitivity(mu) + gb.mu_sensitivity(mu)))
+    return dict(gb=gb, ga=ga, mu=mu, mu_term=mu_term, o2n=o2n, n2o=n2o, lam=lamX, pre=pre, post=post, new_region=new_region, old_region=old_region)
+
+
+def check_accepted_spr1(tally, cov, w, Xn, dvA, dP, k_term, log_mh, rng_before, where):
+    """The identity of an accepted SPR1 move (the module's docstring)."""
+    assert w.t_max_tip is not None, "the watch does not know the run's latest tip time"
+    limit = scan_limit_from_stream(rng_before)
+    d = spr1_identity(w, Xn, dvA, limit)
+    ga, gb, mu, o2n, n2o, lam = d["ga"], d["gb"], d["mu"], d["o2n"], d["n2o"], d["lam"]
+    terms = [ga.delta_log_G, ga.log_alpha_mut(mu), gb.delta_log_G, gb.log_alpha_mut(mu)]
+    lam_term = (lam.n + 8) * X.U * float(lam.S / lam.value) * (o2n.lambda_sensitivity + n2o.lambda_sensitivity)
+    gamma_term = o2n.gamma_term + n2o.gamma_term
+    tag = "%s [%s scan, %d and %d regions, new region %s]" % (where, "unlimited" if limit is None else "limit 1", len(d["pre"].regions), len(d["post"].regions), o2n.branch_kind)
+    # the study's half on its own ...
+    sv = n2o.exact.value - o2n.exact.value
+    # ... and the whole
+    v = (terms[0].value - terms[1].value) - (terms[2].value - terms[3].value) + sv + dP.value
+    S = sum((t.S for t in terms), dP.S + n2o.exact.S + o2n.exact.S)
+    bound = sum(t.bound() for t in terms) + d["mu_term"] + dP.bound() + k_term + n2o.exact.bound() + o2n.exact.bound() + gamma_term + lam_term
+    ex = X.Exact(v, S, 0)
+    tally.check("log_mh_spr1", ex, log_mh, tag, bound - ex.bound())
+    # what is left of log_mh when the exact graft and prior terms are taken away is the engine's log_alpha_n2o - log_alpha_o2n
+    rest = F(log_mh) - ((terms[0].value - terms[1].value) - (terms[2].value - terms[3].value) + dP.value)
+    exs = X.Exact(sv, n2o.exact.S + o2n.exact.S, 0)
+    tally.check("spr1_log_alpha_n2o_less_o2n", exs, rest, tag, bound - exs.bound())
+    for what, e, val in (("log_mh_spr1", ex, log_mh), ("spr1_log_alpha_n2o_less_o2n", exs, rest)):     # how close the worst comes to its bound
+        k = what + " (share of its bound)"
+        tally.worst[k] = max(tally.worst.get(k, 0.0), e.err(val) / bound)
+    cov.accepted_spr1_log_mh_exact += 1
+    B = w.dv.T
+    new_r, old_r = d["pre"].regions[d["new_region"]], d["post"].regions[d["old_region"]]
+    nreg = max(len(d["pre"].regions), len(d["post"].regions))
+    hits = (limit is None, new_r.above_root and o2n.branch_kind == "gamma", new_r.above_root and o2n.branch_kind == "power", old_r.above_root,
+            not w.includes_root, new_r.m >= 1, new_r.uncounted >= 1, nreg > 64, nreg > 640)
+    for i, hit in enumerate(hits):
+        cov.accepted_spr1_classes[i] += int(bool(hit))
+    return d
+
+
 def run_stepped(tally, cov, engine, sc, parts, incl, ref, ev, pop, steps, tag="", watch=None, advance=advance_one_move):
     """Step a configured engine `steps` times and check every move of the watched parts (default: all)."""
     ids = list(range(len(parts))) if watch is None else list(watch)
@@ -533,6 +665,7 @@ def run_stepped(tally, cov, engine, sc, parts, incl, ref, ev, pop, steps, tag=""
     def on_step(p, s, before, after):
         if p not in watches:
             watches[p] = PartWatch(p, before, ref, ev, pop, incl[p], tag)
+            watches[p].t_max_tip = sc.t_max_tip
         check_step(tally, cov, watches[p], s, before, after)
     step_chain(engine, ids, steps, on_step, advance)
     return watches

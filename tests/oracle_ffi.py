@@ -33,7 +33,7 @@ def lib():
             "orc_part_get_derived": [E, C.c_int, P(dbl), P(C.c_int), P(dbl), P(dbl)],
             "orc_part_get_coalescent": [E, C.c_int, P(C.c_int), P(dbl), P(dbl), P(dbl), P(dbl), P(C.c_int), P(dbl), P(dbl)],
             "orc_part_get_stats": [E, C.c_int, P(_PartStatsC)], "orc_part_get_trace": [E, C.c_int, P(C.c_int), P(dbl)],
-            "orc_part_check": [E, C.c_int, C.c_char_p, C.c_int],
+            "orc_part_check": [E, C.c_int, C.c_char_p, C.c_int], "orc_part_rng": [E, C.c_int, P(u64), P(u64), P(u64), P(i32)],
             "orc_Ttwiddle_l": [E, C.c_int, P(dbl)], "orc_num_muts_l": [E, P(C.c_int)], "orc_scalable_log_prior": [E, C.c_int, dbl, dbl, P(dbl)],
             "orc_tree_query": [E, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)],
             "orc_debug_graft": [E, C.c_int, C.c_int, dbl, C.c_int, C.c_int, dbl, P(dbl), C.c_int, P(C.c_int)], "orc_part_log_G": [E, C.c_int, P(dbl), P(dbl)], "orc_debug_edit": [E, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int), P(dbl), P(dbl), P(C.c_int)],
@@ -215,6 +215,12 @@ class OracleEngine:
     def part_stats(self, part):
         s = _PartStatsC(); self.L.orc_part_get_stats(self.h, part, C.byref(s))
         return dict(status=s.status, num_nodes=s.num_nodes, moves_done=s.moves_done, proposed=list(s.proposed), accepted=list(s.accepted), rng_draws=s.rng_draws)
+
+    def part_rng(self, part) -> dict:
+        """Where the part's Philox stream stands, as EmatBackend.part_rng reports it."""
+        k, c, sp, hs = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int32()
+        self._ck(self.L.orc_part_rng(self.h, part, C.byref(k), C.byref(c), C.byref(sp), C.byref(hs)), "part_rng")
+        return dict(key=int(k.value), counter=int(c.value), spare=int(sp.value), has_spare=bool(hs.value))
 
     def part_trace(self, part, cap):
         n = C.c_int(cap); tr = np.zeros((max(cap, 1), 4))

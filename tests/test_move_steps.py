@@ -7,6 +7,11 @@ tests/graft_model.py, the slide's Hastings factor and the exact prior difference
 along the same branch, 4 up past an ancestor and 2 down past the sibling with two or more branches to choose from, 4 of a child
 of the run's root, 25 in parts without the run's root; Coverage.assert_conditions requires at least one of each kind.
 
+An accepted SPR1 move's whole log_mh is another (move_steps.check_accepted_spr1: the same graft numbers, the exact prior difference and
+log_alpha_n2o - log_alpha_o2n of the two candidate studies of tests/study_model.py, at the scan limit read from the part's random stream).
+Over CASES the oracle proposes 297 SPR1 moves and accepts 178, every one of which goes through it (asserted); the rare kinds -- unlimited
+scans, root changes, large studies -- are test_study_model.py's.
+
 What a rejected topology move gives back, as this file establishes on the oracle (check_step asserts it of every rejected
 subtree slide and SPR1 move of these cases; Coverage counts them): mutation times BIT FOR BIT, except on the sibling branch of a
 subtree pruned from under the run's root (reflected about the root's time and back: held to four roundings); lambda_i bit for

@@ -3,7 +3,8 @@ EmatBackend with the parts staged in LDS and resident in HBM (use_lds), large pa
 and the parts cut by kernels from the tree resident in HBM, across two cycles.  tests/move_steps.py has the identities and
 the bounds; like the oracle, the device must give back mutation times bit for bit after a rejected topology move (the
 subtree pruned from under the run's root aside) and holds the lambda_i it recomputed to their exact bounds.  Every accepted
-subtree slide, in every one of these runs, is held to the exact log_mh of move_steps.check_accepted_slide.
+subtree slide, in every one of these runs, is held to the exact log_mh of move_steps.check_accepted_slide, and every accepted SPR1 move
+to that of move_steps.check_accepted_spr1 (the candidate studies of tests/study_model.py).
 
 The same conditions as in test_move_steps.py keep the file honest, over all its cases."""
 import numpy as np
