@@ -60,6 +60,7 @@ emat_status emat_debug_pop(emat_backend* h, const emat_pop_model* pm, int32_t op
   for (int i = 0; i < 4; ++i) pt.p[i] = hp.p[i];
   pt.t_c = hp.t_c; pt.skygrid_x = dx.p; pt.skygrid_gamma = dg.p;
   pt.skygrid_inv_dx = (hp.x.size() >= 2 && hp.x.back() > hp.x.front()) ? (double)(hp.x.size() - 1) / (hp.x.back() - hp.x.front()) : 0.0;
+  pt.skygrid_x0 = hp.x.empty() ? 0.0 : hp.x.front();
   hipLaunchKernelGGL(k_debug_pop, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, pt, (int)op, da.p, db.p, dout.p, (int)n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));

@@ -851,26 +851,69 @@ EMAT_DF double uniform_f64(double v) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
   return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
-EMAT_DF double skygrid_log_N_uniform(const EMAT_CONST_AS PopTable* p, double t) {   // skygrid_interval + skygrid_log_N
-  const EMAT_CONST_AS double* x = uniform_const_ptr((const double*)p->skygrid_x);
-  const EMAT_CONST_AS double* ga = uniform_const_ptr((const double*)p->skygrid_gamma);
-  const int n = p->skygrid_num_knots, M = n - 1;
-  const double g = (t - x[0]) * p->skygrid_inv_dx;
-  int k = __builtin_amdgcn_readfirstlane(g > 0.0 ? (g < (double)n ? (int)g : n) : 0);   // NaN -> 0
+// The Skygrid's log N(t_new) - log N(t_old) in two scalar round trips.  Load by load -- the table's fields, x[0] through the pointer
+// just loaded, a knot per loop test, the gammas, for one time and then for the other -- it was nine, each behind the one before, for a
+// dozen f64 operations.  Here the first trip takes kind and everything fixed that log N(t) starts from as ONE load, the table's first
+// sixteen words (emat_slab.hpp; x[0] is among them, PopTable::skygrid_x0; read field by field, the fields wanted only where kind == 2
+// are loaded there, a trip behind kind).  Both times' knot intervals are guessed from it, and the second trip takes, for both times
+// at once, the two knots the loops' first tests compare with and the two gammas the value is formed from: x and gamma at
+// max(k - 1, 0) and min(k, n - 1), inside the arrays whatever k is.  A guess whose first tests end both loops IS the loops'
+// result, and the value is formed from what is loaded: same operands, same order.  Any other guess goes through the loops as before.
+//
+// The guess: skygrid_interval's (int)g is the number of knots BELOW a time that lies between two knots of an even grid, and the
+// interval wanted, lower_bound, is one more -- its second loop always takes one step.  The batch has no step to spare, its loads
+// being asked for before any knot is seen, so it guesses (int)g + 1: lower_bound itself for every time of an even grid that is not
+// on a knot.  (The loops end at lower_bound from any start: the guess decides which loads are made, never the result.)
+typedef uint32_t PopHeadWords __attribute__((ext_vector_type(16)));
+typedef PopHeadWords PopHead __attribute__((aligned(8)));   // (a PopTable is aligned as its doubles are)
+EMAT_DF int skygrid_guess_uniform(double t, double x0, double inv_dx, int n) {
+  const double g = (t - x0) * inv_dx;
+  return __builtin_amdgcn_readfirstlane(g > 0.0 ? (g < (double)n ? (int)g + 1 : n) : 0);   // NaN -> 0; (int)g <= n - 1 where it is taken
+}
+struct SkyKnots { double xa, xb, ga, gb; int k; };   // x and gamma at max(k - 1, 0) and at min(k, n - 1)
+EMAT_DF SkyKnots skygrid_knots_uniform(const EMAT_CONST_AS double* x, const EMAT_CONST_AS double* ga, int n, int k) {
+  const int a = k - 1 > 0 ? k - 1 : 0, hi = n - 1 > 0 ? n - 1 : 0, b = k < hi ? k : hi;
+  SkyKnots s; s.xa = x[a]; s.xb = x[b]; s.ga = ga[a]; s.gb = ga[b]; s.k = k;
+  return s;
+}
+// All eight values are in registers here, behind one wait: left to itself the compiler moves each load down to the test that first
+// looks at it (x[k] only where x[k - 1] < t held, the gammas only where the guess stood), one round trip after the other again.
+EMAT_DF void skygrid_knots_arrive(SkyKnots& a, SkyKnots& b) {
+  asm volatile("" : "+s"(a.xa), "+s"(a.xb), "+s"(a.ga), "+s"(a.gb), "+s"(b.xa), "+s"(b.xb), "+s"(b.ga), "+s"(b.gb));
+}
+EMAT_DF double skygrid_log_N_uniform(const EMAT_CONST_AS double* x, const EMAT_CONST_AS double* ga, int n, int type, double t, const SkyKnots& s) {   // skygrid_interval + skygrid_log_N
+  int k = s.k; const int M = n - 1;
+  if ((k == 0 || s.xa < t) && (k == n || !(s.xb < t))) {   // the first test of each loop below: k is lower_bound
+    if (k == 0) return s.ga;        // ga[0]
+    if (k > M) return s.gb;         // ga[M]
+    if (type == 1) return s.gb;     // ga[k]
+    const double cc = (t - s.xa) / (s.xb - s.xa);
+    return (1 - cc) * s.ga + cc * s.gb;
+  }
   while (k > 0 && !(x[k - 1] < t)) --k;
   while (k < n && x[k] < t) ++k;
   if (k == 0) return ga[0];
   if (k > M) return ga[M];
-  if (p->skygrid_type == 1) return ga[k];
+  if (type == 1) return ga[k];
   const double cc = (t - x[k - 1]) / (x[k] - x[k - 1]);
   return (1 - cc) * ga[k - 1] + cc * ga[k];
 }
 EMAT_DF double log_pop_ratio_uniform(const PopTable* pp, double t_new, double t_old) {
   const EMAT_CONST_AS PopTable* p = uniform_const_ptr(pp);
-  const int kind = p->kind;
+  const PopHead w = *(const EMAT_CONST_AS PopHead*)p;
+  const int kind = (int)w[0];
   if (kind == 0) return 0.0;
   t_new = uniform_f64(t_new); t_old = uniform_f64(t_old);
-  if (kind == 2) return skygrid_log_N_uniform(p, t_new) - skygrid_log_N_uniform(p, t_old);
+  if (kind == 2) {
+    const int type = (int)w[1], n = (int)w[2];
+    const double inv_dx = __builtin_bit_cast(double, ((uint64_t)w[5] << 32) | w[4]), x0 = __builtin_bit_cast(double, ((uint64_t)w[11] << 32) | w[10]);
+    const EMAT_CONST_AS double* x = (const EMAT_CONST_AS double*)(((uint64_t)w[7] << 32) | w[6]);
+    const EMAT_CONST_AS double* ga = (const EMAT_CONST_AS double*)(((uint64_t)w[9] << 32) | w[8]);
+    SkyKnots at_new = skygrid_knots_uniform(x, ga, n, skygrid_guess_uniform(t_new, x0, inv_dx, n));
+    SkyKnots at_old = skygrid_knots_uniform(x, ga, n, skygrid_guess_uniform(t_old, x0, inv_dx, n));
+    skygrid_knots_arrive(at_new, at_old);
+    return skygrid_log_N_uniform(x, ga, n, type, t_new, at_new) - skygrid_log_N_uniform(x, ga, n, type, t_old, at_old);
+  }
   const double t0 = p->p[0], n0 = p->p[1], gr = p->p[2], floor_n = p->p[3];
   double a = n0 * m_exp((t_new - t0) * gr); a = floor_n > a ? floor_n : a;
   double b = n0 * m_exp((t_old - t0) * gr); b = floor_n > b ? floor_n : b;

@@ -41,6 +41,7 @@ emat_status sync_model_to_device(emat_backend* h) {
   for (int i = 0; i < 4; ++i) pt.p[i] = B.pop.p[i];
   pt.t_c = B.pop.t_c; pt.skygrid_x = B.d_sky_x.p; pt.skygrid_gamma = B.d_sky_g.p;
   pt.skygrid_inv_dx = (B.pop.x.size() >= 2 && B.pop.x.back() > B.pop.x.front()) ? (double)(B.pop.x.size() - 1) / (B.pop.x.back() - B.pop.x.front()) : 0.0;
+  pt.skygrid_x0 = B.pop.x.empty() ? 0.0 : B.pop.x.front();
   HIP_TRY(B.d_pop.upload(&pt, 1));
   B.model_dirty = false;
   return EMAT_OK;

@@ -74,6 +74,7 @@ PopTable probe_pop_table(const HostPopModel& hp, const double* sky_x, const doub
   pt.t_c = hp.t_c;
   pt.skygrid_x = sky_x; pt.skygrid_gamma = sky_g;
   pt.skygrid_inv_dx = (hp.x.size() >= 2 && hp.x.back() > hp.x.front()) ? (double)(hp.x.size() - 1) / (hp.x.back() - hp.x.front()) : 0.0;
+  pt.skygrid_x0 = hp.x.empty() ? 0.0 : hp.x.front();
   return pt;
 }
 // "" or why the model cannot be built: a Skygrid without its knots, or what its constructor refuses.

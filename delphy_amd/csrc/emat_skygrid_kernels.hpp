@@ -70,7 +70,7 @@ struct SkygridArgs {
 __device__ __forceinline__ PopTable sky_pop_table(const SkygridArgs& a, const double* x, const double* gamma) {
   PopTable pt{};
   pt.kind = 2; pt.skygrid_type = a.type; pt.skygrid_num_knots = a.num_knots; pt.skygrid_inv_dx = a.inv_dx;
-  pt.skygrid_x = x; pt.skygrid_gamma = gamma;
+  pt.skygrid_x = x; pt.skygrid_gamma = gamma; pt.skygrid_x0 = a.num_knots > 0 ? x[0] : 0.0;
   return pt;
 }
 

@@ -15,6 +15,7 @@
 #ifndef EMAT_SLAB_HPP_
 #define EMAT_SLAB_HPP_
 
+#include <cstddef>
 #include <cstdint>
 
 namespace emat {
@@ -181,12 +182,16 @@ struct PopTable {               // reference Pop_model family (core/pop_model.h)
   int32_t skygrid_type;
   int32_t skygrid_num_knots;
   int32_t pad;
-  double p[4];
-  double t_c;                   // Exp_pop_model::t_c_
+  // (kind and everything the Skygrid's log N(t) starts from lie in the table's first 64 bytes: the moves take them with one load)
   double skygrid_inv_dx;        // (knots - 1) / (x_last - x_first): first guess of the knot interval of a time (0 if degenerate)
   const double* skygrid_x;
   const double* skygrid_gamma;
+  double skygrid_x0;            // skygrid_x[0], for that guess without a load through the pointer (0 without knots)
+  double p[4];
+  double t_c;                   // Exp_pop_model::t_c_
 };
+static_assert(offsetof(PopTable, kind) == 0 && offsetof(PopTable, skygrid_type) == 4 && offsetof(PopTable, skygrid_num_knots) == 8 && offsetof(PopTable, skygrid_inv_dx) == 16 &&
+              offsetof(PopTable, skygrid_x) == 24 && offsetof(PopTable, skygrid_gamma) == 32 && offsetof(PopTable, skygrid_x0) == 40 && sizeof(PopTable) >= 64, "log_pop_ratio_uniform (emat_device_core.hpp) reads these as the table's first sixteen words");
 
 struct RunFlags {
   double t_max_tip;
