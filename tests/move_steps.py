@@ -25,8 +25,13 @@ to the identities the move code implies (emat_device_moves.hpp; the reference's 
   (old sibling, old t_P) in the study scanned from the new one, both on the tree with X's graft read off (asserted to be the same tree
   before and after), at the scan limit the move's second draw gave.  The limit is read from the part's random stream before the move:
   its first word through mix_draw must say SPR1 (asserted), its second through to_co is below 0.01 for an unlimited scan.  The model is
-  evaluated at that limit only.  What the move DREW (the region and the time in it) is not held to anything here: the pick depends on
-  the depth-first order, which only the algorithm defines;
+  evaluated at that limit only;
+- what every move DREW -- the kind, the node picks, the number of words it consumed, its acceptance, the bounded exponential, the
+  Gaussian step, the slide's pick among straddling branches, a reform's new mutation times, the time inside an SPR1 region -- is held, by
+  the probability integral transform, to the exact inverse CDF at the very uniforms of the part's random stream: tests/draws_model.py has
+  the identities and their bounds, check_step calls it for every move.  Which region an SPR1's cumulative walk picks is not held (it
+  depends on the depth-first order, which only the algorithm defines; its probability is held through log_alpha), nor are the draws of
+  the mutational-history sampler (the density of the history written is) or a compound reform's inner move.
 
 Bounds.  A log_mh or an increment is held to the `Exact.bound()` of the difference, whose S holds only the terms that differ
 (exact_model's docstring).  Added to it, each named:
@@ -66,9 +71,9 @@ from fractions import Fraction as F
 
 import numpy as np
 
+import draws_model as DM
 import exact_model as X
 import graft_model as GM
-import skygrid_streams as RS
 import study_model as SM
 
 KINDS = ("inner_node_displace", "tip_displace", "branch_reform", "subtree_slide", "spr1")
@@ -240,7 +245,9 @@ class Coverage:
     FIELDS = ("steps", "accepted", "accepted_root_displacements", "accepted_negative_log_mh", "accepted_while_grid_grew",
               "accepted_reform_same_site_twice", "accepted_reform_more_than_32", "accepted_outside_root_part", "compound", "compound_accepted",
               "rejected_topology", "rejected_rooty_not_bit_identical", "rejected_topology_lambda_not_bit_identical", "unchecked",
-              "accepted_slides_log_mh_exact", "accepted_slide_kinds", "accepted_spr1_log_mh_exact", "accepted_spr1_classes")
+              "accepted_slides_log_mh_exact", "accepted_slide_kinds", "accepted_spr1_log_mh_exact", "accepted_spr1_classes",
+              "draws_held", "borderline", "slope_sign_undetermined", "position_half_known", "draws_verdicts_drawn", "draws_bexp", "draws_bexp_outside_root_part", "draws_gaussian_root",
+              "draws_gaussian_slide", "draws_slide_down_picks", "draws_grid_cells", "draws_reforms", "draws_spr1_times", "draws_early_end", "draws_ends_at_once")
     SLIDE_KINDS = ("same branch", "up with n >= 2", "down with n >= 2", "X under the run's root", "X in a part without the run's root")
     SPR1_CLASSES = ("unlimited scan", "new region above the root, gamma", "new region above the root, power law", "old region above the root",
                     "part without the run's root", "min_muts >= 1 in the new region", "uncounted mutation on the path", "more than 64 regions",
@@ -257,6 +264,15 @@ class Coverage:
         self.accepted_slide_kinds = [0] * len(self.SLIDE_KINDS)       # accepted slides held to the identity, per SLIDE_KINDS
         self.accepted_spr1_log_mh_exact = 0
         self.accepted_spr1_classes = [0] * len(self.SPR1_CLASSES)     # accepted SPR1 moves held to the identity, per SPR1_CLASSES
+        # tests/draws_model.py: moves whose every identity held; the three ways a step may be left out of one; per class
+        self.draws_held = self.borderline = self.slope_sign_undetermined = self.position_half_known = self.draws_verdicts_drawn = 0
+        self.draws_bexp = [0] * len(DM.BEXP_CLASSES)                  # accepted bounded-exponential draws held, per exact ltr class
+        self.draws_bexp_outside_root_part = [0] * len(DM.BEXP_CLASSES)    # ... of them in parts without the run's root (the simple moves are compiled once for each kind of part)
+        self.draws_gaussian_root = self.draws_gaussian_slide = self.draws_slide_down_picks = self.draws_grid_cells = 0
+        self.draws_reforms = [0] * len(DM.REFORM_SIZES)               # accepted reforms whose new times were held
+        self.draws_spr1_times = [0] * len(DM.SPR1_TIMES)
+        self.draws_early_end = [0] * len(DM.EARLY)
+        self.draws_ends_at_once = [0] * 6     # exact tip, reform of the root, reform of an empty branch: in the root part (the move is called), outside it (settled in the frame)
 
     def add(self, o):
         for f in self.FIELDS:
@@ -279,6 +295,22 @@ class Coverage:
         assert self.accepted_slides_log_mh_exact == self.accepted[3], d      # every accepted slide was held to the identity
         assert self.accepted_slides_log_mh_exact >= 1 and min(self.accepted_slide_kinds) >= 1, (dict(zip(self.SLIDE_KINDS, self.accepted_slide_kinds)), d)
         assert self.accepted_spr1_log_mh_exact == self.accepted[4], d        # every accepted SPR1 move was held to the identity
+        # what the moves drew (tests/draws_model.py).  The minimums are what the CPU oracle does on test_move_steps.py's cases; a class the
+        # oracle reaches a few times asks for one step.  (The bounded exponential's other classes of ltr are test_draws_model.py's.)
+        named = lambda names, counts: (dict(zip(names, counts)), d)
+        assert self.borderline == 0 and self.slope_sign_undetermined == 0 and self.draws_held == self.steps, d
+        assert self.position_half_known == 0, d      # no step was held under the weaker two-readings rule: none of these runs stops a pass for room
+        assert self.draws_verdicts_drawn >= 3274, d
+        assert self.draws_bexp[2] >= 1582 and self.draws_bexp[3] >= 2282, named(DM.BEXP_CLASSES, self.draws_bexp)
+        assert self.draws_gaussian_root == self.accepted_root_displacements and self.draws_gaussian_slide == self.accepted[3], d
+        assert self.draws_slide_down_picks >= 1 and self.draws_grid_cells >= 817, d
+        assert min(self.draws_reforms) >= 1 and self.draws_reforms[0] >= 576 and self.draws_reforms[4] >= 216, named(DM.REFORM_SIZES, self.draws_reforms)
+        assert sum(self.draws_spr1_times) == self.accepted[4] and self.draws_spr1_times[0] >= 173 and self.draws_spr1_times[2] >= 1, named(DM.SPR1_TIMES, self.draws_spr1_times)
+        # (no valid part has fewer than 3 nodes; a bounded exponential that lands on a bound is test_draws_model.py's case `on-a-bound`; no
+        # SPR1 of any case drew a time that equals an end of its region)
+        reached = [c for i, c in enumerate(self.draws_early_end) if i not in (4, 5, 11)]
+        assert min(reached) >= 1 and self.draws_early_end[3] >= 3301, named(DM.EARLY, self.draws_early_end)
+        assert min(self.draws_ends_at_once) >= 1, d                          # in the root part (a move is called) and outside it (settled in the frame)
 
 
 class PartWatch:
@@ -293,6 +325,7 @@ class PartWatch:
         self.kbf = np.array([abs(float(k)) for k in self.kb])      # |k_bar_p| as floats, for the allowance's kmax
         self.moves = 0          # since k_bar_p was built from scratch
         self.t_max_tip = None   # the run's latest tip time (the studies above the root need it); run_stepped sets it
+        self.topology = True    # whether the engine was configured with topology moves (the draw that picks the move spans 32, else 30)
         assert_valid_part(first["tree"], ref)
 
     def k_allowance(self, tab):
@@ -337,6 +370,8 @@ def check_step(tally, cov, w: PartWatch, step, b, a):
             fails.append("%s: trace row %s" % (where, a["row"])); cov.unchecked += 1
             return
         where += " (%s of node %d, %s, log_mh %r)" % (KINDS[kind], node, "accepted" if acc else "not accepted", log_mh)
+        compound = kind == 2 and w.includes_root and node >= 0 and node != tb.root and int(tb.parent[node]) == tb.root
+        DM.check_draws(tally, cov, DM.Step(w, b, a, kind, node, log_mh == log_mh, acc, log_mh, compound, 32.0 if w.topology else 30.0, w.topology), where)
         dp = [y - x for x, y in zip(b["stats"]["proposed"], a["stats"]["proposed"])]
         da = [y - x for x, y in zip(b["stats"]["accepted"], a["stats"]["accepted"])]
         if dp != [int(k == kind) for k in range(5)] or da != [int(k == kind and acc) for k in range(5)]:
@@ -349,7 +384,6 @@ def check_step(tally, cov, w: PartWatch, step, b, a):
         if grew > 0:
             w.kb.extend([F(1)] * grew)          # appended cells hold the lineage above the root and nothing else
             w.kbf = np.concatenate([w.kbf, np.ones(grew)])
-        compound = kind == 2 and w.includes_root and node >= 0 and node != tb.root and int(tb.parent[node]) == tb.root
         nb = len(tabb["k_bar_p"])
 
         if not acc and not compound:
@@ -500,6 +534,9 @@ def check_step(tally, cov, w: PartWatch, step, b, a):
         cov.unchecked += 1
 
 
+straddling_branches = DM.straddling_branches     # (the one derivation: a slide's alpha_ratio here, its pick of the new sibling there)
+
+
 def slide_alpha_ratio(B, A, Xn):
     """(alpha_ratio, kind, n) of the subtree slide that took tree B to tree A (exact_model._Tree) by moving X: from the tree before,
     X and the new time of X's parent.  kind: "same", "up" or "down"; n: the branches the slide chose among on its way back (up) or
@@ -510,17 +547,7 @@ def slide_alpha_ratio(B, A, Xn):
     SS = [k for k in A.kids[P] if k != Xn][0]
     old_t, new_t = B.t[P], A.t[P]
 
-    def straddling(top, t):         # branches below `top` that hold time t, X's subtree pruned
-        out, st = [], [top]
-        while st:
-            v = st.pop()
-            if v == Xn:
-                continue
-            if t <= B.t[v]:
-                out.append(v)
-            else:
-                st += B.kids[v]
-        return out
+    straddling = lambda top, t: straddling_branches(B, top, t, Xn)
     if SS == S:
         G = B.parent[P]
         assert new_t < min(B.t[Xn], B.t[S]) and (G < 0 or B.t[G] <= new_t), "the new time is not on the branch above X's sibling"
@@ -576,20 +603,12 @@ def scan_limit_from_stream(rng, mix_total=32.0):
                 pass
         assert len(out) == 1, "the stream's position is known to a half block only, and the two readings give %s" % sorted(map(str, out))
         return out.pop()
-    key, ctr = np.uint64(rng["key"]), int(rng["counter"])
-    if rng["has_spare"]:                    # the second half of the block opened last is the next word
-        blk = RS.philox4x32_10(np.uint64(ctr - 1), key)
-        w1 = int(blk[2]) | (int(blk[3]) << 32)
-        assert rng["spare"] is None or w1 == int(rng["spare"]), "the stream's pending half block is not the second half of block %d" % (ctr - 1)
-        blk = RS.philox4x32_10(np.uint64(ctr), key)
-        w2 = int(blk[0]) | (int(blk[1]) << 32)
-    else:
-        blk = RS.philox4x32_10(np.uint64(ctr), key)
-        w1, w2 = int(blk[0]) | (int(blk[1]) << 32), int(blk[2]) | (int(blk[3]) << 32)
-    r = 0.0 + (mix_total - 0.0) * float(RS.to_co(np.uint64(w1)))
-    assert r >= mix_total - 1.0, "the move's first draw %r does not pick SPR1" % r
-    chooser = float(RS.to_co(np.uint64(w2)))
-    return None if chooser < 0.01 else 1
+    try:
+        W = DM.Words(rng)           # (the one reader of the stream: draws_model holds the rest of the move's words to their identities)
+    except DM.Mismatch as e:
+        raise AssertionError(str(e))
+    assert DM.kind_of(W[0], mix_total) == 4, "the move's first draw does not pick SPR1"
+    return None if DM.to_co(W[1]) < F(0.01) else 1
 
 
 def spr1_identity(w, Xn, dvA, limit):
@@ -645,6 +664,7 @@ def check_accepted_spr1(tally, cov, w, Xn, dvA, dP, k_term, log_mh, rng_before, 
         k = what + " (share of its bound)"
         tally.worst[k] = max(tally.worst.get(k, 0.0), e.err(val) / bound)
     cov.accepted_spr1_log_mh_exact += 1
+    DM.check_spr1_time(tally, cov, w, Xn, d, limit, rng_before, tag)
     B = w.dv.T
     new_r, old_r = d["pre"].regions[d["new_region"]], d["post"].regions[d["old_region"]]
     nreg = max(len(d["pre"].regions), len(d["post"].regions))
@@ -655,7 +675,7 @@ def check_accepted_spr1(tally, cov, w, Xn, dvA, dP, k_term, log_mh, rng_before, 
     return d
 
 
-def run_stepped(tally, cov, engine, sc, parts, incl, ref, ev, pop, steps, tag="", watch=None, advance=advance_one_move):
+def run_stepped(tally, cov, engine, sc, parts, incl, ref, ev, pop, steps, tag="", watch=None, advance=advance_one_move, topology=True):
     """Step a configured engine `steps` times and check every move of the watched parts (default: all)."""
     ids = list(range(len(parts))) if watch is None else list(watch)
     if hasattr(engine, "synchronize"):
@@ -665,7 +685,7 @@ def run_stepped(tally, cov, engine, sc, parts, incl, ref, ev, pop, steps, tag=""
     def on_step(p, s, before, after):
         if p not in watches:
             watches[p] = PartWatch(p, before, ref, ev, pop, incl[p], tag)
-            watches[p].t_max_tip = sc.t_max_tip
+            watches[p].t_max_tip, watches[p].topology = sc.t_max_tip, topology
         check_step(tally, cov, watches[p], s, before, after)
     step_chain(engine, ids, steps, on_step, advance)
     return watches

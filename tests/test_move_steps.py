@@ -16,7 +16,10 @@ What a rejected topology move gives back, as this file establishes on the oracle
 subtree slide and SPR1 move of these cases; Coverage counts them): mutation times BIT FOR BIT, except on the sibling branch of a
 subtree pruned from under the run's root (reflected about the root's time and back: held to four roundings); lambda_i bit for
 bit in most of them, and within its Exact bound where the hops or the rooty graft recomputed it.  test_move_steps_gpu.py asserts
-the same of the device."""
+the same of the device.
+
+Every move's draws are held to tests/draws_model.py in the same check_step; Coverage.assert_conditions names the classes and the counts
+the oracle reaches over CASES.  DRAW_CASES are the two cases that reach what CASES do not (test_draws_model.py runs them)."""
 import numpy as np
 import pytest
 
@@ -49,6 +52,84 @@ def high_mutation_scenario():
     return sc, nu
 
 
+def steep_scenario():
+    """21 nodes by hand, 64 sites under Jukes-Cantor at mu = 2^-7 (lambda = 1/2 everywhere).  Two cherries whose nodes have 200 to 400
+    days between their parents and their tips (the exact ltr = lambda (b - a) of their displacement is 100 to 200) and whose tips may lie
+    anywhere in the 300 days after them (theirs about -150), under a node S that the partition's rule can cut at (a part needs ten nodes
+    on either side), so that the steep windows lie in a part WITHOUT the run's root: the copy of the simple moves that is the hot path.
+    Above S a ladder of day-long branches with exact-date tips (ltr in between).  Long windows need long branches, and a history sampled
+    along one holds lambda T mutations: the branches next to the run's root, which a branch reform re-samples, are a day long, and the
+    topology moves are off."""
+    from delphy_amd.scenarios import Scenario
+    L = ZERO_SLOPE_SITES
+    big = 3.4028234663852886e38
+    # (name, time, children or None for an exact-date tip, or the (t_min, t_max) of an uncertain one)
+    wide = (-400.0, 300.0)
+    sub = ("S", -400.0, [("C", -200.0, [("A", 0.0, wide), ("B", 0.0, wide)]),
+                         ("M", -399.5, [("M2", -399.3, [("C2", -200.0, [("A2", 0.0, wide), ("B2", 0.0, wide)]), ("T2", -399.1, None)]), ("T", -399.0, None)])])
+    top = sub
+    for k in range(4, -1, -1):          # the ladder: N4 .. N1 and the root, each with an exact-date tip half a day later
+        top = ("N%d" % k, -405.0 + k, [top, ("Q%d" % k, -404.5 + k, None)])
+    rows = []
+
+    def walk(node, parent):
+        i = len(rows)
+        rows.append([parent, -1, -1, node[1], -big, big])
+        if isinstance(node[2], list):
+            rows[i][1], rows[i][2] = walk(node[2][0], i), walk(node[2][1], i)
+        else:
+            rows[i][4], rows[i][5] = node[2] if node[2] else (node[1], node[1])
+        return i
+    walk(top, -1)
+    t = d.FlatTree.empty(len(rows), 0, 0, 0)
+    t.root = 0
+    for i, (par, c0, c1, time, lo, hi) in enumerate(rows):
+        t.parent[i], t.child0[i], t.child1[i], t.t[i], t.t_min[i], t.t_max[i] = par, c0, c1, time, lo, hi
+    ref = np.random.default_rng(2).integers(0, 4, L).astype(np.uint8)
+    return Scenario("two cherries on long stalks", t, ref, 300.0, 2.0 ** -7, 1.0, (0.25, 0.25, 0.25, 0.25), d.PopModel.const(200.0), L)
+
+
+def on_a_bound_scenario():
+    """Two tips by hand whose parent, the run's root, lies one double before them: tip A's date may be anywhere in the ten days before 100,
+    so its window is (t_root, 100], two doubles wide, and every time its bounded exponential draws rounds to one end of it: the move ends
+    un-noted after the pick and one word.  A population of 2^-40 makes the prior refuse every step of the root further back (the two
+    lineages would coexist longer: -1e12 in log per day), so the window stays what it is."""
+    from delphy_amd.scenarios import Scenario
+    L = ZERO_SLOPE_SITES
+    t = d.FlatTree.empty(3, 0, 0, 0)
+    t.root = 0
+    t.child0[0], t.child1[0] = 1, 2
+    t.parent[1] = t.parent[2] = 0
+    t.t[:] = (np.nextafter(100.0, -np.inf), 100.0, 100.0)
+    big = 3.4028234663852886e38
+    t.t_min[:] = (-big, 90.0, 100.0); t.t_max[:] = (big, 100.0, 100.0)
+    ref = np.random.default_rng(3).integers(0, 4, L).astype(np.uint8)
+    return Scenario("a tip one double below its parent", t, ref, 101.0, 2.0 ** -7, 1.0, (0.25, 0.25, 0.25, 0.25), d.PopModel.const(2.0 ** -40), L)
+
+
+ZERO_SLOPE_SITES = 64
+
+
+def zero_slope_scenario():
+    """Three tips by hand: the two tips of a cherry miss complementary halves of the sites, the third is an outgroup.  Just below the
+    cherry node every site is missing under one child or the other, so d log G / dt of its time is lambda - lambda: the Fraction 0 exactly,
+    and with a mutation rate of 2^-10 under Jukes-Cantor the engines' maintained doubles cancel to 0.0 too (the uniform branch)."""
+    from delphy_amd.scenarios import Scenario
+    L = ZERO_SLOPE_SITES
+    t = d.FlatTree.empty(5, 0, 2, 0)
+    t.root = 0
+    t.child0[0], t.child1[0] = 1, 2
+    t.child0[1], t.child1[1] = 3, 4
+    t.parent[1] = t.parent[2] = 0; t.parent[3] = t.parent[4] = 1
+    t.t[:] = (-100.0, -50.0, 0.0, 0.0, 0.0)
+    big = 3.4028234663852886e38
+    t.t_min[:] = (-big, -big, 0.0, 0.0, 0.0); t.t_max[:] = (big, big, 0.0, 0.0, 0.0)
+    t.miss_offset[:] = (0, 0, 0, 0, 1, 2)
+    t.miss_start[:] = (0, L // 2); t.miss_end[:] = (L // 2, L)
+    ref = np.random.default_rng(1).integers(0, 4, L).astype(np.uint8)
+    return Scenario("cherry of complementary halves", t, ref, 0.0, 2.0 ** -10, 1.0, (0.25, 0.25, 0.25, 0.25), d.PopModel.const(50.0), L)
+
+
 def _case(name):
     """name -> (scenario, nu_l, evo, num_parts, seed, t_step factor, steps).  Step counts and seeds are chosen so that the
     conditions of Coverage.assert_conditions hold over the file on the oracle."""
@@ -66,22 +147,31 @@ def _case(name):
         return sc, nu, None, 1, {"a": 11, "b": 12}[name[-1]], 1.0, STEPS[name]
     if name == "fine-grid":
         return make_scenario("C1", num_tips=40, num_sites=1000, uncertain_tips=0.3, seed=77), None, None, 2, 13, 1.0 / 8, STEPS[name]
+    if name == "steep":
+        return steep_scenario(), None, None, 2, 2, None, STEPS[name]      # (seed 2: the partition cuts at S)
+    if name == "on-a-bound":
+        return on_a_bound_scenario(), None, None, 1, 7, None, STEPS[name]
+    if name == "zero-slope":
+        return zero_slope_scenario(), None, None, 1, 3, None, STEPS[name]
     raise KeyError(name)
 
 
 STEPS = {"C1/1": 500, "C1/6": 250, "C2/1": 120, "C2/6": 100, "C3/1": 30, "C3/6": 40, "random": 150,
-         "high-mutation/a": 350, "high-mutation/b": 300, "fine-grid": 500}
+         "high-mutation/a": 350, "high-mutation/b": 300, "fine-grid": 500, "steep": 300, "zero-slope": 200, "on-a-bound": 150}
 CASES = ["C1/1", "C1/6", "C2/1", "C2/6", "C3/1", "C3/6"] + ["random%d" % k for k in range(12)] + ["high-mutation/a", "high-mutation/b", "fine-grid"]
+# what CASES do not reach of the draws (tests/draws_model.py): test_draws_model.py runs these on the oracle, test_draws_model_gpu.py on the device
+DRAW_CASES = ["steep", "zero-slope", "on-a-bound"]
+TOPOLOGY_OFF = ("steep", "on-a-bound")      # (the draw that picks the move spans 30 there)
 _done = {}
 
 
 def prepare(name):
     sc, nu_l, evo, nparts, seed, tf, steps = _case(name)
     parts, incl, seeds, root_part, ref = split_parts(sc, nparts, seed)
-    t_step = sc.default_t_step() * tf
+    t_step = sc.default_t_step() * tf if tf is not None else 1.0
 
     def setup(engine):
-        configure(engine, sc, ref, parts, incl, seeds, root_part, t_step, nu_l=nu_l, evo=evo)
+        configure(engine, sc, ref, parts, incl, seeds, root_part, t_step, topology=name not in TOPOLOGY_OFF, nu_l=nu_l, evo=evo)
         return engine
     return sc, parts, incl, ref, X.Evo.of(sc, nu_l, evo), X.Pop(sc.pop), steps, setup
 
@@ -92,7 +182,7 @@ def run_case(name, make_engine, who, steps_divisor=1):
     tally, cov = Tally(who), M.Coverage()
     eng = setup(make_engine(sc.num_sites, steps + 8))
     try:
-        M.run_stepped(tally, cov, eng, sc, parts, incl, ref, ev, pop, steps, tag=name)
+        M.run_stepped(tally, cov, eng, sc, parts, incl, ref, ev, pop, steps, tag=name, topology=name not in TOPOLOGY_OFF)
     finally:
         eng.close()
     return tally, cov

@@ -5,6 +5,9 @@ the bounds; like the oracle, the device must give back mutation times bit for bi
 subtree pruned from under the run's root aside) and holds the lambda_i it recomputed to their exact bounds.  Every accepted
 subtree slide, in every one of these runs, is held to the exact log_mh of move_steps.check_accepted_slide, and every accepted SPR1 move
 to that of move_steps.check_accepted_spr1 (the candidate studies of tests/study_model.py).
+What every one of these moves drew -- kind, picks, words consumed, acceptance, the bounded exponential, the Gaussian step, the slide's
+pick, a reform's new times, an SPR1's time in its region -- goes through tests/draws_model.py in the same check_step, with the oracle's
+counts per class as the device's minimums (Coverage.assert_conditions).
 
 The same conditions as in test_move_steps.py keep the file honest, over all its cases."""
 import numpy as np

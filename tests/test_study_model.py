@@ -287,6 +287,10 @@ def assert_lean_conditions(done, record_property):
     record_property("held", total.accepted_spr1_log_mh_exact)
     print("accepted SPR1 moves held to the identity:", total.accepted_spr1_log_mh_exact, got)
     assert total.unchecked == 0
+    # the time every one of them drew in its new region was held to the region's inverse CDF (tests/draws_model.py), the rare regions too
+    times = dict(zip(M.DM.SPR1_TIMES, total.draws_spr1_times))
+    record_property("spr1_times_held", times)
+    assert total.borderline == 0 and total.position_half_known == 0 and sum(total.draws_spr1_times) == total.accepted_spr1_log_mh_exact and min(total.draws_spr1_times) >= 1, times
     for c, need in REQUIRED.items():
         assert total.accepted_spr1_classes[c] >= need, (C[c], need, got)
 
