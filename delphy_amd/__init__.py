@@ -18,6 +18,8 @@ from .engine import (  # noqa: F401
     SamplesProbe,
     SkygridMovesResult,
     SkygridSpec,
+    SubstMovesResult,
+    SubstSpec,
     SynthParams,
     TipDescs,
     build_library,

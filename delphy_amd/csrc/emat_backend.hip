@@ -37,6 +37,7 @@
 #include "emat_site_rate_kernels.hpp"   // the site-rate moves: steps on alpha and the Gibbs draw of every nu_l
 #include "emat_skygrid_kernels.hpp"     // the Skygrid population moves: tau, the zero mode and the HMC on the gammas
 #include "emat_exp_pop_kernels.hpp"     // the Exponential population moves: n0 and the growth rate
+#include "emat_subst_kernels.hpp"       // the substitution-model moves: mu, the HKY frequencies and kappa
 #include "emat_state_host.hpp"      // buffers, host records, emat_backend and the transitions of its part state
 #include "emat_slab_host.hpp"       // slab codec, geometry, size classes
 #include "emat_pass_host.hpp"       // materialize, launch_moves, finish_pass, the two pulls
@@ -645,3 +646,4 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 #include "emat_coal_stats_host.hpp"
 #include "emat_skygrid_host.hpp"
 #include "emat_exp_pop_host.hpp"
+#include "emat_subst_host.hpp"

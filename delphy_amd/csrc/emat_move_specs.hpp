@@ -1,6 +1,7 @@
 // emat_move_specs.hpp -- what a global-move spec must satisfy before any model is looked at: one function per spec, the text of the first fault or nullptr.
 //
-// No HIP in here: the backend's entry points (emat_skygrid_host.hpp, emat_exp_pop_host.hpp) and the run driver's setters (emat_run.cpp) both refuse with these texts.
+// No HIP in here: the backend's entry points (emat_skygrid_host.hpp, emat_exp_pop_host.hpp, emat_subst_host.hpp) and the run driver's setters (emat_run.cpp) both refuse
+// with these texts.  Also hky_derive_q, the q of an HKY model, which both derive.
 #ifndef EMAT_MOVE_SPECS_HPP_
 #define EMAT_MOVE_SPECS_HPP_
 
@@ -28,6 +29,32 @@ inline const char* exp_pop_spec_fault(const emat_exp_pop_spec& s, const double* 
   if (!std::isfinite(s.inv_n0_prior_beta)) return "inv_n0_prior_beta must be finite";
   if (s.rounds < 0) return "rounds must not be negative";
   return nullptr;
+}
+
+// The substitution-model moves (emat_subst_host.hpp; the run driver's setter, which brings its own model, passes with_model = false).
+constexpr int k_subst_max_rounds = 4096;
+inline const char* subst_spec_fault(const emat_subst_spec& s, bool with_model = true) {
+  if (with_model) {
+    if (!finite_positive(s.mu)) return "mu must be finite and positive";
+    if (!finite_positive(s.kappa)) return "kappa must be finite and positive";
+    double sum = 0.0;
+    for (int a = 0; a < 4; ++a) { if (!(s.pi[a] > 0.0 && s.pi[a] < 1.0)) return "every pi[a] must lie inside (0, 1)"; sum += s.pi[a]; }
+    if (!(std::fabs(sum - 1.0) <= 1e-9)) return "the pi[a] must add up to 1 within 1e-9";
+  }
+  if (!std::isfinite(s.mu_prior_alpha)) return "mu_prior_alpha must be finite";
+  if (!std::isfinite(s.mu_prior_beta)) return "mu_prior_beta must be finite";
+  if (s.rounds < 0) return "rounds must not be negative";
+  return nullptr;
+}
+
+// q of the HKY model (kappa, pi): Hky_model::derive_site_evo_model (reference evo_hky.cpp:7-50), statement for statement what the run
+// driver's push_model has always sent -- the model a handle holds after the substitution-model moves is the one the next push sends.
+inline void hky_derive_q(double kappa, const double pi[4], double q[16]) {
+  const double k = kappa;
+  double r[4][4] = {{0, 1, k, 1}, {1, 0, 1, k}, {k, 1, 0, 1}, {1, k, 1, 0}};
+  double rowv[4]; for (int b = 0; b < 4; ++b) { rowv[b] = 0.0; for (int a = 0; a < 4; ++a) rowv[b] += pi[a] * r[a][b]; }
+  double R = 0.0; for (int b = 0; b < 4; ++b) R += rowv[b] * pi[b];
+  for (int a = 0; a < 4; ++a) { q[a * 4 + a] = 0.0; for (int b = 0; b < 4; ++b) if (a != b) { q[a * 4 + b] = r[a][b] / R * pi[b]; q[a * 4 + a] -= q[a * 4 + b]; } }
 }
 
 }  // namespace emat

@@ -53,6 +53,7 @@ struct RunDriver {
   bool have_pop = false; emat_pop_model pop{}; std::vector<double> sky_x, sky_g;
   bool skygrid_moves_on = false; emat_skygrid_spec sky_spec{}; uint64_t skygrid_rounds = 0;   // Run's Skygrid settings with skygrid_tau_, and how many rounds of the Skygrid moves have drawn a key
   bool exp_pop_moves_on = false; emat_exp_pop_spec xp_spec{}; uint64_t exp_pop_rounds = 0;      // Run's Exp_pop_model settings, and how many rounds of the Exponential moves have drawn a key
+  bool subst_moves_on = false; emat_subst_spec sb_spec{}; uint64_t subst_rounds = 0;            // Run's mu prior and switches (the model is hky_* above), and how many rounds of the substitution-model moves have drawn a key
   double t_step = 1.0; bool t_step_set = false;
   int only_displacing_inner_nodes = 0, topology_moves_enabled = 1;
   bool reference_remainder = false;   // the remainder of count / parts goes to part 0 as in Run::run_local_moves (run.cpp:683-689), instead of one move per part
@@ -184,12 +185,9 @@ struct RunDriver {
     if (!have_hky) return fail(EMAT_ERR_STATE, "emat_run_set_hky must be called first");
     EMAT_TRY(bk(emat_set_ref_sequence(backend, ref.data(), L)));
     // Hky_model::derive_site_evo_model (evo_hky.cpp:7-50)
-    const double k = hky_kappa; const double* pi = hky_pi;
-    double r[4][4] = {{0, 1, k, 1}, {1, 0, 1, k}, {k, 1, 0, 1}, {1, k, 1, 0}};
-    double rowv[4]; for (int b = 0; b < 4; ++b) { rowv[b] = 0.0; for (int a = 0; a < 4; ++a) rowv[b] += pi[a] * r[a][b]; }
-    double R = 0.0; for (int b = 0; b < 4; ++b) R += rowv[b] * pi[b];
+    const double* pi = hky_pi;
     double q[16];
-    for (int a = 0; a < 4; ++a) { q[a * 4 + a] = 0.0; for (int b = 0; b < 4; ++b) if (a != b) { q[a * 4 + b] = r[a][b] / R * pi[b]; q[a * 4 + a] -= q[a * 4 + b]; } }
+    hky_derive_q(hky_kappa, pi, q);   // (emat_move_specs.hpp: the backend derives the same q after its substitution-model moves)
     std::vector<int32_t> pfs(L, 0);
     std::vector<double> nu = nu_l.empty() ? std::vector<double>(L, 1.0) : nu_l;
     EMAT_TRY(bk(emat_set_evo(backend, 1, &hky_mu, pi, q, nu.data(), pfs.data())));
@@ -422,7 +420,7 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // ---- The global moves: three groups (site rates, Skygrid, Exponential population), one owner for each rule they share.
+  // ---- The global moves: four groups (substitution model, site rates, Skygrid, Exponential population), one owner for each rule they share.
   static constexpr const char* kShardedStatistics = "a sharded run gathers the part lengths and sums S, R across ranks itself (see emat_backend.h)";
   static constexpr uint64_t kSiteRateKeyTag = 0x5349544552415445ull;   // "SITERATE"
   // One round of a group: the key from the group's counter under its tag, the caller's trace buffer handed through, the counter bumped only when the backend did the round.
@@ -450,6 +448,23 @@ struct RunDriver {
     site_rate_alpha = res.alpha;
     nu_l.resize((size_t)L);
     EMAT_TRY(bk(emat_get_nu_l(backend, nu_l.data())));
+    if (out) *out = res;
+    return EMAT_OK;
+  }
+
+  // Run::mu_move, then sb_spec.rounds times hky_frequencies_move + hky_kappa_move (run.cpp:703-719), on the device from the statistics of the parts out
+  // there, which never leave it (emat_parts_subst_moves).  The accepted model becomes the run's: the backend holds it already, the next push sends it again.
+  static constexpr uint64_t kSubstKeyTag = 0x5355425354303031ull;   // "SUBST001"
+  emat_status subst_moves(emat_subst_result* out) {
+    EMAT_TRY(need_backend());
+    EMAT_TRY(need_parts_out());
+    if (!tree_cut) return fail(EMAT_ERR_STATE, "the substitution-model moves read the parts: repartition first");
+    if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
+    emat_subst_spec spec = sb_spec;
+    spec.mu = hky_mu; spec.kappa = hky_kappa; for (int a = 0; a < 4; ++a) spec.pi[a] = hky_pi[a];
+    emat_subst_result res{};
+    EMAT_TRY(keyed_round(subst_rounds, kSubstKeyTag, out, res, [&](uint64_t key) { return emat_parts_subst_moves(backend, &spec, key, &res); }));
+    hky_mu = res.mu; hky_kappa = res.kappa; for (int a = 0; a < 4; ++a) hky_pi[a] = res.pi[a];
     if (out) *out = res;
     return EMAT_OK;
   }
@@ -518,7 +533,7 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // One cycle after another (run.cpp:622-657; of the global moves, the site-rate, the Skygrid and the Exponential groups when they are on)
+  // One cycle after another (run.cpp:622-657; of the global moves, the substitution-model, the site-rate, the Skygrid and the Exponential groups when they are on)
   emat_status do_mcmc_steps(int64_t steps, int64_t per_cycle) {
     EMAT_TRY(need_backend());
     if (shard_world > 1) return fail(EMAT_ERR_STATE, "a sharded run is cycled by its caller, who owns the collectives (see emat_host.h)");
@@ -529,6 +544,7 @@ struct RunDriver {
       if (exp_pop_moves_on) EMAT_TRY(exp_pop_moves(nullptr));   // likewise
       EMAT_TRY(repartition());
       laps.lap(); laps.mark("cycle: 1 repartition");
+      if (subst_moves_on) EMAT_TRY(subst_moves(nullptr));           // groups 1 and 2 of run_global_moves, before the site rates as there (run.cpp:703-732)
       if (site_rate_moves_on) EMAT_TRY(site_rate_moves(nullptr));   // where the reference runs its global moves (run.cpp:635-641)
       const int64_t k = std::min(per_cycle, steps - done);
       EMAT_TRY(run_moves(k));
@@ -838,6 +854,18 @@ emat_status emat_run_get_exp_pop(emat_run* r, double* n0, double* g) {
   if (!r->d.have_pop || r->d.pop.kind != EMAT_POP_EXP) return r->d.fail(EMAT_ERR_STATE, "emat_run_get_exp_pop: the run has no exponential population model");
   if (n0) *n0 = r->d.pop.p[1];
   if (g) *g = r->d.pop.p[2];
+  return EMAT_OK;
+}
+emat_status emat_run_set_subst_moves(emat_run* r, int32_t on, const emat_subst_spec* spec) {   // (mu, kappa and pi of the spec are ignored: the run's own are used)
+  return set_moves_spec(r, "emat_run_set_subst_moves: ", on, spec, [](const emat_subst_spec& s) { return s.rounds > k_subst_max_rounds ? "rounds must not exceed 4096" : subst_spec_fault(s, false); }, &RunDriver::subst_moves_on, &RunDriver::sb_spec);
+}
+emat_status emat_run_subst_moves(emat_run* r, emat_subst_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.subst_moves(out); }
+emat_status emat_run_get_hky(emat_run* r, double* mu, double* kappa, double* pi) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!r->d.have_hky) return r->d.fail(EMAT_ERR_STATE, "emat_run_get_hky: emat_run_set_hky must be called first");
+  if (mu) *mu = r->d.hky_mu;
+  if (kappa) *kappa = r->d.hky_kappa;
+  if (pi) std::copy(r->d.hky_pi, r->d.hky_pi + 4, pi);
   return EMAT_OK;
 }
 emat_status emat_run_get_site_rates(emat_run* r, double* alpha, double* nu_l) {

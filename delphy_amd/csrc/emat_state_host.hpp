@@ -175,6 +175,12 @@ struct ExpPopScratch {
   DevBuf<emat_exp_pop_step> trace;
 };
 
+// What the substitution-model moves work in (emat_subst_kernels.hpp, emat_subst_host.hpp): the statistics record, the result, the trace; grow-only.
+struct SubstScratch {
+  DevBuf<double> stats, result;
+  DevBuf<emat_subst_step> trace;
+};
+
 // What the site-rate moves work in (emat_site_rate_kernels.hpp, emat_site_rate_host.hpp): grow-only, sized by the handle's L at the first call.
 struct SiteRateScratch {
   DevBuf<double> T, nu_new, d_log_G, d_prior, result; DevBuf<int32_t> M;
@@ -315,6 +321,7 @@ struct emat_backend {
   SkygridScratch sky;               // what emat_skygrid_moves works in
   ExpPopScratch xp;                 // what emat_exp_pop_moves works in
   SiteRateScratch sr;               // what emat_site_rate_moves works in
+  SubstScratch sb;                  // what emat_subst_moves works in
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
   int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs

@@ -261,6 +261,74 @@ class ExpPopMovesResult:
     trace: Optional[np.ndarray]    # [2 * rounds] records of EXP_POP_STEP_DTYPE (even: n0 steps, odd: g steps), or None when not asked for
 
 
+class _SubstSpecC(C.Structure):
+    _fields_ = [("mu", C.c_double), ("kappa", C.c_double), ("pi", C.c_double * 4), ("mu_prior_alpha", C.c_double), ("mu_prior_beta", C.c_double),
+                ("do_mu", C.c_int32), ("do_pi", C.c_int32), ("do_kappa", C.c_int32), ("rounds", C.c_int32)]
+
+
+class _SubstStepC(C.Structure):
+    _fields_ = [("kappa", C.c_double), ("pi", C.c_double * 4), ("proposal", C.c_double), ("delta_log_G", C.c_double), ("log_prior_ratio", C.c_double),
+                ("log_metropolis", C.c_double), ("u", C.c_double), ("ia", C.c_int32), ("ib", C.c_int32), ("accepted", C.c_int32), ("evaluated", C.c_int32),
+                ("left_unit", C.c_int32), ("force_rejected", C.c_int32)]
+
+
+class _SubstResultC(C.Structure):
+    _fields_ = [("mu", C.c_double), ("kappa", C.c_double), ("pi", C.c_double * 4), ("mu_post_shape", C.c_double), ("mu_post_rate", C.c_double), ("mu_draw", C.c_double),
+                ("delta_log_G", C.c_double), ("delta_log_other_priors", C.c_double), ("mu_delta_log_G", C.c_double), ("mu_delta_log_other_priors", C.c_double),
+                ("pi_accepted", C.c_int32), ("kappa_accepted", C.c_int32), ("pi_left_unit", C.c_int32), ("forced_rejections", C.c_int32),
+                ("trace", C.POINTER(_SubstStepC)), ("trace_capacity", C.c_int32)]
+
+
+SUBST_STEP_DTYPE = np.dtype([("kappa", "f8"), ("pi", "f8", (4,)), ("proposal", "f8"), ("delta_log_G", "f8"), ("log_prior_ratio", "f8"), ("log_metropolis", "f8"), ("u", "f8"),
+                             ("ia", "i4"), ("ib", "i4"), ("accepted", "i4"), ("evaluated", "i4"), ("left_unit", "i4"), ("force_rejected", "i4")])
+_SUBST_TRACE = (_SubstResultC, _SubstStepC, SUBST_STEP_DTYPE)   # ... and one of the substitution-model moves (steps = 2 * rounds)
+
+
+@dataclass
+class SubstSpec:
+    """The settings of the substitution-model moves (include/emat_backend.h: emat_subst_spec) with the linked HKY model they start from; the
+    defaults of the prior, the switches and the rounds are the reference's."""
+    mu: float = 1e-3
+    kappa: float = 1.0
+    pi: Sequence[float] = (0.25, 0.25, 0.25, 0.25)
+    mu_prior_alpha: float = 1.0
+    mu_prior_beta: float = 0.0
+    do_mu: bool = True
+    do_pi: bool = True
+    do_kappa: bool = True
+    rounds: int = 10
+
+    def c_struct(self) -> "_SubstSpecC":
+        return _SubstSpecC(float(self.mu), float(self.kappa), (C.c_double * 4)(*[float(v) for v in self.pi]), float(self.mu_prior_alpha), float(self.mu_prior_beta),
+                           int(self.do_mu), int(self.do_pi), int(self.do_kappa), int(self.rounds))
+
+
+@dataclass
+class SubstMovesResult:
+    """What emat_subst_moves returns (include/emat_backend.h: emat_subst_result)."""
+    mu: float
+    kappa: float
+    pi: np.ndarray                 # [4]
+    mu_post_shape: float
+    mu_post_rate: float
+    mu_draw: float
+    delta_log_G: float
+    delta_log_other_priors: float
+    mu_delta_log_G: float
+    mu_delta_log_other_priors: float
+    pi_accepted: int
+    kappa_accepted: int
+    pi_left_unit: int
+    forced_rejections: int
+    trace: Optional[np.ndarray]    # [2 * rounds] records of SUBST_STEP_DTYPE (even: pi steps, odd: kappa steps), or None when not asked for
+
+
+def _subst_result(res: "_SubstResultC", trace) -> "SubstMovesResult":
+    r = _traced_result(SubstMovesResult, res, trace)
+    r.pi = np.array(list(res.pi), np.float64)
+    return r
+
+
 @dataclass
 class SamplesProbe:
     """What emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors return (include/emat_backend.h: emat_samples_probe_result).
@@ -547,6 +615,9 @@ def load_library():
         "emat_tree_skygrid_moves": [B, P(_PopModelC), P(_SkygridSpecC), dbl, dbl, u64, P(_SkygridResultC)],
         "emat_exp_pop_moves": [B, P(_PopModelC), P(_ExpPopSpecC), dbl, dbl, i32, i32, P(dbl), i32, P(dbl), u64, P(_ExpPopResultC)],
         "emat_tree_exp_pop_moves": [B, P(_PopModelC), P(_ExpPopSpecC), dbl, dbl, u64, P(_ExpPopResultC)],
+        "emat_subst_moves": [B, P(_SubstSpecC), i32, P(dbl), P(i64), P(i64), u64, P(_SubstResultC)], "emat_parts_subst_stats": [B, P(dbl), P(i64), P(i64)],
+        "emat_parts_subst_moves": [B, P(_SubstSpecC), u64, P(_SubstResultC)], "emat_get_evo": [B, P(i32), P(dbl), P(dbl), P(dbl)],
+        "emat_run_set_subst_moves": [R, i32, P(_SubstSpecC)], "emat_run_subst_moves": [R, P(_SubstResultC)], "emat_run_get_hky": [R, P(dbl), P(dbl), P(dbl)],
         "emat_run_set_exp_pop_moves": [R, i32, P(_ExpPopSpecC)], "emat_run_exp_pop_moves": [R, P(_ExpPopResultC)], "emat_run_get_exp_pop": [R, P(dbl), P(dbl)],
         "emat_run_set_skygrid_moves": [R, i32, P(_SkygridSpecC)], "emat_run_skygrid_moves": [R, P(_SkygridResultC)], "emat_run_get_skygrid": [R, P(dbl), P(dbl)],
         "emat_run_set_site_rate_moves": [R, i32, dbl], "emat_run_site_rate_moves": [R, P(_SiteRateResultC)], "emat_run_get_site_rates": [R, P(dbl), P(dbl)],
@@ -1262,6 +1333,48 @@ class EmatBackend:
         """emat_exp_pop_moves on the statistics of the tree resident in HBM, which never leave it (emat_tree_exp_pop_moves)."""
         return self.exp_pop_moves(pop, spec, t_ref, t_step, 0, None, None, key, trace)
 
+    def subst_moves(self, spec: "SubstSpec", Ttwiddle_beta_a, num_muts_beta_ab, root_state_counts, key: int = 0, trace: bool = False) -> "SubstMovesResult":
+        """mu_move, then `spec.rounds` times hky_frequencies_move + hky_kappa_move on the device (include/emat_backend.h: emat_subst_moves), from the
+        run's summed statistics: Ttwiddle_beta_a [P][4], num_muts_beta_ab [P][4][4] and the state counts at the run's root [4]."""
+        T = np.ascontiguousarray(Ttwiddle_beta_a, np.float64); M = np.ascontiguousarray(num_muts_beta_ab, np.int64); Cn = np.ascontiguousarray(root_state_counts, np.int64)
+        T = T.reshape(-1, 4); nP = T.shape[0]
+        if M.size != 16 * nP or Cn.size != 4:
+            raise ValueError("num_muts_beta_ab must be [P][4][4] for the P of Ttwiddle_beta_a, root_state_counts [4]")
+        sp = spec.c_struct()
+        res, tr = _traced_result_c(*_SUBST_TRACE, 2 * spec.rounds, trace)
+        self._ck(self._lib.emat_subst_moves(self._h, C.byref(sp), nP, T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int64)), Cn.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            int(key) & _KEY_MASK, C.byref(res)), "emat_subst_moves")
+        return _subst_result(res, tr)
+
+    def parts_subst_stats(self, num_partitions: Optional[int] = None):
+        """(Ttwiddle_beta_a [P][4], num_muts_beta_ab [P][4][4], root_state_counts [4]) of the parts on this handle, reduced on the device (emat_parts_subst_stats).
+        The call writes for the P of the handle's model, so the arrays are sized by it (emat_get_evo); `num_partitions`, when given, must be that P."""
+        n = C.c_int32(0)
+        self._ck(self._lib.emat_get_evo(self._h, C.byref(n), None, None, None), "emat_get_evo")
+        if num_partitions is not None and int(num_partitions) != n.value:
+            raise ValueError("num_partitions is %d, the handle's model has %d site partitions" % (num_partitions, n.value))
+        num_partitions = n.value
+        T = np.zeros((num_partitions, 4)); M = np.zeros((num_partitions, 4, 4), np.int64); Cn = np.zeros(4, np.int64)
+        self._ck(self._lib.emat_parts_subst_stats(self._h, T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int64)), Cn.ctypes.data_as(C.POINTER(C.c_int64))),
+                 "emat_parts_subst_stats")
+        return T, M, Cn
+
+    def parts_subst_moves(self, spec: "SubstSpec", key: int = 0, trace: bool = False) -> "SubstMovesResult":
+        """emat_subst_moves on the statistics of the parts on this handle, which never leave it (emat_parts_subst_moves)."""
+        sp = spec.c_struct()
+        res, tr = _traced_result_c(*_SUBST_TRACE, 2 * spec.rounds, trace)
+        self._ck(self._lib.emat_parts_subst_moves(self._h, C.byref(sp), int(key) & _KEY_MASK, C.byref(res)), "emat_parts_subst_moves")
+        return _subst_result(res, tr)
+
+    def get_evo(self):
+        """(mu [P], pi [P][4], q [P][4][4]) of the model the handle holds (emat_get_evo)."""
+        n = C.c_int32(0); dp = C.POINTER(C.c_double)
+        self._ck(self._lib.emat_get_evo(self._h, C.byref(n), None, None, None), "emat_get_evo")
+        nP = n.value
+        mu = np.zeros(nP); pi = np.zeros((nP, 4)); q = np.zeros((nP, 4, 4))
+        self._ck(self._lib.emat_get_evo(self._h, C.byref(n), mu.ctypes.data_as(dp), pi.ctypes.data_as(dp), q.ctypes.data_as(dp)), "emat_get_evo")
+        return mu, pi, q
+
     def debug_pop_gradient(self, pop: PopModel, op: int, k: int, a, b) -> np.ndarray:
         """Test hook: the device's d log(integral of N over [a, b]) / d gamma_k (op 3) / d log N(a) / d gamma_k (op 4), point by point."""
         a = np.ascontiguousarray(a, np.float64); b = np.ascontiguousarray(b, np.float64); out = np.zeros_like(a)
@@ -1537,6 +1650,25 @@ class EmatRun:
         res, tr = _traced_result_c(*_EXP_POP_TRACE, 2 * getattr(self, "_xp_rounds", 0), trace)
         self._ck(self._lib.emat_run_exp_pop_moves(self._h, C.byref(res)), "emat_run_exp_pop_moves")
         return _traced_result(ExpPopMovesResult, res, tr)
+
+    def set_subst_moves(self, on: bool = True, spec: "SubstSpec" = None):
+        """The substitution-model moves once per cycle of do_mcmc_steps, after the repartition and before the site-rate round (off by default); `spec`: Run's
+        mu prior, the three switches and the rounds (its mu, kappa and pi are ignored: the run's own are used)."""
+        sp = (spec or SubstSpec()).c_struct()
+        self._ck(self._lib.emat_run_set_subst_moves(self._h, 1 if on else 0, C.byref(sp)), "emat_run_set_subst_moves")
+        self._sb_rounds = int(sp.rounds)
+
+    def subst_moves(self, trace: bool = False) -> "SubstMovesResult":
+        """One call of the substitution-model moves while the parts are out (emat_run_subst_moves): the mu draw, then `rounds` times the pi step and the kappa step."""
+        res, tr = _traced_result_c(*_SUBST_TRACE, 2 * getattr(self, "_sb_rounds", 0), trace)
+        self._ck(self._lib.emat_run_subst_moves(self._h, C.byref(res)), "emat_run_subst_moves")
+        return _subst_result(res, tr)
+
+    def hky(self):
+        """(mu, kappa, pi [4]) as the driver holds them."""
+        mu, kappa = C.c_double(), C.c_double(); pi = np.zeros(4)
+        self._ck(self._lib.emat_run_get_hky(self._h, C.byref(mu), C.byref(kappa), pi.ctypes.data_as(C.POINTER(C.c_double))), "emat_run_get_hky")
+        return mu.value, kappa.value, pi
 
     def exp_pop(self):
         """(n0, g) of the exponential population model as the driver holds them."""

@@ -756,6 +756,85 @@ emat_status emat_exp_pop_moves(emat_backend* h, const emat_pop_model* pop_model,
  * emat_exp_pop_moves returns when fed the arrays that call hands out.  Its refusals are emat_exp_pop_moves' own, then the tree's state. */
 emat_status emat_tree_exp_pop_moves(emat_backend* h, const emat_pop_model* pop_model, const emat_exp_pop_spec* spec, double t_ref, double t_step, uint64_t key, emat_exp_pop_result* out);
 
+/* ---- the substitution-model moves: mu, the HKY frequencies and kappa -----------------------------------------------------------
+ * replaces: groups 1 and 2 of Run::run_global_moves (reference run.cpp:703-719): mu_move (:781-821), then `rounds` times
+ * hky_frequencies_move (:953-1034) and hky_kappa_move (:1036-1103), on the device (csrc/emat_subst_kernels.hpp) in ONE launch of one
+ * workgroup: the Gibbs draw of mu, then the steps s = 0 .. 2 rounds - 1, even s a frequencies step and odd s a kappa step.  The model is
+ * the linked HKY model of `spec` (the reference refuses unlinked ones, :791-795); every step derives q from (kappa, pi) as
+ * Hky_model::derive_site_evo_model does (evo_hky.cpp:7-50).
+ *
+ * Inputs are the statistics of the WHOLE run, as SUMS over all handles, exactly as emat_site_rate_moves takes its own: Ttwiddle_beta_a and
+ * num_muts_beta_ab as emat_get_global_stats hands them out (num_muts is the sum of the counts off the diagonal), and
+ * root_state_counts[a], the number of sites present in state a at the run's root: the reference sequence's counts less the root's
+ * deltas and missations (:996-1004), summed over the site partitions.
+ *
+ *   mu draw (when do_mu)  mu ~ Gamma(shape = num_muts + mu_prior_alpha, rate = sum_{beta, a} q_a Ttwiddle_beta_a + mu_prior_beta), the
+ *                         sampler of emat_debug_sample_gamma; delta log G = -(new - old) Ttwiddle + num_muts log(new / old), the other
+ *                         priors grow by (alpha - 1) log(new / old) - beta (new - old) (:818-820).
+ *   pi step (:964-1033)   d = 0.01 u0, ia = floor(4 u1), ib = (ia + 1 + floor(3 u2)) mod 4 (the law of the reference's redraw loop);
+ *                         pi[ia] += d, pi[ib] -= d; a pi that leaves (0, 1) ends the step at once (:977-979, counted in pi_left_unit).
+ *                         delta log G = the three sums over branch lengths, root counts and mutations; no prior ratio, no Hastings term.
+ *   kappa step (:1049-1102) scale = 0.75 + (1 / 0.75 - 0.75) u0, kappa *= scale; delta log G = the two sums over branch lengths and mutations;
+ *                         log_prior_ratio = log of :1064-1067 (log-normal, mean 1, sigma 1.25), Hastings term log(old / new) (:1091).
+ *   both                  force_reject as :1007, :1016, :1084 (a count above 0 against a rate or frequency of 0: the step is evaluated, never
+ *                         accepted, counted in forced_rejections, and reports 0 for its three sums); else accepted when log_metropolis > 0 ||
+ *                         u < exp(log_metropolis) (a NaN rejects).  A disabled move's step does nothing but keeps its draws.
+ * The 16 (a, b) terms of a step are formed by 16 lanes and added in the reference's order; no atomics: the same arguments give the same
+ * result BIT FOR BIT on every handle and in every call.
+ *
+ * Random numbers: the (key, id) streams of the site-rate moves under the next two pseudo-ids below the Exponential moves' one:
+ *   0xFFFFFFF8  the mu draw, from the stream's start (drawn also when do_mu is 0, provided shape and rate are positive)
+ *   0xFFFFFFF7  step s takes the stream's 64-bit words 4 s .. 4 s + 3, all in [0, 1): a pi step u0, u1, u2 and the acceptance uniform; a
+ *               kappa step u0 and the acceptance uniform (words 2 and 3 unused).  A step's draws depend on (key, s) alone.
+ *
+ * The call first finishes a pending pass.  Afterwards the handle's model is the new one, as if given to emat_set_evo: mu for every
+ * partition, pi, and q derived from the returned kappa and pi on the host (hky_derive_q, csrc/emat_move_specs.hpp, the run driver's own
+ * arithmetic); nu_l, the site partitions and the reference sequence are untouched and nothing L-long is uploaded.
+ *
+ *   emat_parts_subst_stats   the three statistics from the parts on this handle: k_global_stats' rows reduced on the device in a fixed
+ *                            order (one workgroup per column, 256 threads), the root counts from the root part's root node.
+ *   emat_parts_subst_moves   emat_subst_moves on those statistics without their leaving HBM: bit for bit what emat_subst_moves returns
+ *                            when fed the arrays emat_parts_subst_stats hands out.
+ *   emat_get_evo             the model the handle holds (*num_partitions: in the room of the arrays, out the model's P).
+ *
+ * EMAT_ERR_INVALID_ARGUMENT (text in emat_last_error naming the first offender), all answered before the device is asked for: a null
+ * pointer; mu or kappa not finite or <= 0; a pi[a] outside (0, 1) or |sum - 1| > 1e-9; mu_prior_alpha or mu_prior_beta not finite; rounds
+ * < 0; a trace with trace_capacity < 2 rounds; num_partitions other than emat_set_evo's; a Ttwiddle that is negative or not finite; a
+ * negative count; shape <= 0 or rate <= 0 for the mu draw while do_mu is set.  EMAT_ERR_CAPACITY: more than 4 site partitions, or rounds
+ * > 4 096.  EMAT_ERR_STATE: before emat_set_evo; for the parts calls, with no parts out or no root part on this handle.
+ * EMAT_ERR_NO_DEVICE: a handle without a device, after these checks.  After any refusal the model is untouched and the next call works. */
+typedef struct emat_subst_spec {
+  double mu, kappa, pi[4];                   /* the linked HKY model the moves start from */
+  double mu_prior_alpha, mu_prior_beta;      /* reference run.h:47-50; defaults 1 and 0 */
+  int32_t do_mu, do_pi, do_kappa;            /* which of the moves run */
+  int32_t rounds;                            /* 10 in the reference (run.cpp:714); 0 = the mu draw alone */
+} emat_subst_spec;
+typedef struct emat_subst_step {
+  double kappa, pi[4];                       /* held before the step */
+  double proposal;                           /* d (a pi step, run.cpp:965) or scale (a kappa step, :1050) */
+  double delta_log_G;                        /* :985-1020, :1070-1088; 0 when not evaluated or force-rejected */
+  double log_prior_ratio;                    /* log of :1064-1067; 0 for a pi step */
+  double log_metropolis, u;                  /* :1022, :1091; u in [0, 1) */
+  int32_t ia, ib;                            /* a pi step's two letters (:966-970); -1, -1 for a kappa step */
+  int32_t accepted, evaluated;               /* evaluated = 0: the move is disabled or a pi left (0, 1) */
+  int32_t left_unit, force_rejected;         /* :977-979; :1007, :1016, :1084 */
+} emat_subst_step;
+typedef struct emat_subst_result {
+  double mu, kappa, pi[4];                   /* after the call */
+  double mu_post_shape, mu_post_rate;        /* run.cpp:808-810 */
+  double mu_draw;                            /* :813; NaN when do_mu is 0 and shape or rate is not positive */
+  double delta_log_G, delta_log_other_priors;          /* of the draw and of every accepted step */
+  double mu_delta_log_G, mu_delta_log_other_priors;    /* :818-820 alone; 0 when do_mu is 0 */
+  int32_t pi_accepted, kappa_accepted, pi_left_unit, forced_rejections;
+  emat_subst_step* trace;                    /* may be NULL: room for 2 * rounds records, step s at [s] */
+  int32_t trace_capacity;                    /* in: records `trace` has room for (>= 2 * rounds) */
+} emat_subst_result;
+emat_status emat_subst_moves(emat_backend* h, const emat_subst_spec* spec, int32_t num_partitions, const double* Ttwiddle_beta_a /*[P][4]*/,
+                             const int64_t* num_muts_beta_ab /*[P][4][4]*/, const int64_t* root_state_counts /*[4]*/, uint64_t key, emat_subst_result* out);
+emat_status emat_parts_subst_stats(emat_backend* h, double* Ttwiddle_beta_a /*[P][4]*/, int64_t* num_muts_beta_ab /*[P][4][4]*/, int64_t* root_state_counts /*[4]*/);
+emat_status emat_parts_subst_moves(emat_backend* h, const emat_subst_spec* spec, uint64_t key, emat_subst_result* out);
+emat_status emat_get_evo(emat_backend* h, int32_t* num_partitions, double* mu /*[P]*/, double* pi /*[P][4]*/, double* q /*[P][4][4]*/);
+
 /* replaces: Run::calc_cur_log_coalescent_prior (reference run.cpp:455-465), i.e. Scalable_coalescent_prior::calc_log_prior
  * (scalable_coalescent.cpp:163-187) with every node displaced to its current time (:88-138): the whole-tree grid prior
  *   - sum_cells t_step kbar (kbar - 1) / (2 Nbar)  -  sum over inner nodes of log N(t),

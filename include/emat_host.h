@@ -11,9 +11,11 @@
  *   Run::run_local_moves (run.cpp:682-693)                 emat_run_moves        -> emat_run_moves_even of the backend (remainder spread over the parts)
  *   Run::reassemble (run.cpp:195-256)                      emat_run_reassemble
  *   Run::do_mcmc_steps without the global moves            emat_run_do_mcmc_steps
- *     (run.cpp:622-657; of the global moves only the site-rate group is built)
+ *     (run.cpp:622-657; the global moves' four groups, each off by default, are further down)
  *   Run::alpha_moves, gibbs_sample_all_nus                 emat_run_site_rate_moves  -> emat_site_rate_moves of the backend
  *     (run.cpp:1105-1235)
+ *   Run::mu_move, hky_frequencies_move, hky_kappa_move     emat_run_subst_moves      -> emat_parts_subst_moves of the backend
+ *     (run.cpp:781-821, :953-1103)
  *
  * Also exports the seeded synthetic-EMAT generator used by the bench and the tests
  * (SURVEY section 8(d) configs C1..C5).
@@ -252,8 +254,27 @@ emat_status emat_run_set_exp_pop_moves(emat_run* r, int32_t on, const emat_exp_p
 emat_status emat_run_exp_pop_moves(emat_run* r, emat_exp_pop_result* out /* may be NULL */);   /* needs the tree assembled */
 emat_status emat_run_get_exp_pop(emat_run* r, double* n0, double* g /* either may be NULL */);
 
-/* repartition -> [push params, site-rate moves when on, local moves, reassemble] per cycle of `local_moves_per_cycle` moves
- * (<= 0: 50 x nodes, the reference default run.cpp:669-672), repartitioning at every cycle boundary. */
+/* The substitution-model moves of a run (Run::mu_move, hky_frequencies_move, hky_kappa_move, reference run.cpp:703-719, :781-821,
+ * :953-1103; emat_parts_subst_moves of emat_backend.h).  Off by default: a run without them keeps the mu, kappa and pi of
+ * emat_run_set_hky for ever, and its cycle's code path is what it was.
+ *   emat_run_set_subst_moves  on / off, and Run's mu prior, the three switches and the number of rounds (10 in the reference).  mu, kappa
+ *                             and pi of the spec are ignored: the run's own are used.  EMAT_ERR_INVALID_ARGUMENT: what emat_subst_moves
+ *                             refuses in the rest of a spec, or more rounds than it holds.
+ *   emat_run_subst_moves      one call while the parts are out, like emat_run_site_rate_moves (EMAT_ERR_STATE on an assembled tree): the
+ *                             statistics of the parts never leave the device; the key of call k is the first word of Philox(counter k,
+ *                             key = run seed ^ a fixed tag of its own).  The accepted mu, kappa and pi become the run's -- the backend
+ *                             holds them already, and the next emat_run_push_params sends the same.  `out` (may be NULL): out->trace may
+ *                             be NULL.  A sharded run is refused as the site-rate moves refuse it.
+ *   emat_run_get_hky          mu, kappa and pi[4] as the run holds them (any pointer may be NULL).
+ * With the group on, emat_run_do_mcmc_steps makes one call per cycle after the repartition and BEFORE the site-rate round, the
+ * reference's order (run.cpp:703-732): the site-rate round's Ttwiddle_l is made from the new q. */
+emat_status emat_run_set_subst_moves(emat_run* r, int32_t on, const emat_subst_spec* spec);
+emat_status emat_run_subst_moves(emat_run* r, emat_subst_result* out /* may be NULL */);   /* needs the parts out */
+emat_status emat_run_get_hky(emat_run* r, double* mu, double* kappa, double* pi /*[4]; any may be NULL */);
+
+/* [Skygrid or Exponential population moves when on] -> repartition -> [push params, substitution-model moves when on, site-rate moves
+ * when on, local moves, reassemble] per cycle of `local_moves_per_cycle` moves (<= 0: 50 x nodes, the reference default
+ * run.cpp:669-672), repartitioning at every cycle boundary. */
 emat_status emat_run_do_mcmc_steps(emat_run* r, int64_t steps, int64_t local_moves_per_cycle);
 
 /* Whole tree out (sizes first). The reference sequence may have been re-referenced to the root
