@@ -14,6 +14,8 @@ from .engine import (  # noqa: F401
     ExpPopSpec,
     FlatTree,
     MccTree,
+    MpoxMovesResult,
+    MpoxSpec,
     PopModel,
     SamplesProbe,
     SkygridMovesResult,

@@ -38,6 +38,7 @@
 #include "emat_skygrid_kernels.hpp"     // the Skygrid population moves: tau, the zero mode and the HMC on the gammas
 #include "emat_exp_pop_kernels.hpp"     // the Exponential population moves: n0 and the growth rate
 #include "emat_subst_kernels.hpp"       // the substitution-model moves: mu, the HKY frequencies and kappa
+#include "emat_mpox_kernels.hpp"        // the APOBEC (mpox) model's moves: Gibbs rounds of mu and rho = mu* / mu
 #include "emat_state_host.hpp"      // buffers, host records, emat_backend and the transitions of its part state
 #include "emat_slab_host.hpp"       // slab codec, geometry, size classes
 #include "emat_pass_host.hpp"       // materialize, launch_moves, finish_pass, the two pulls
@@ -647,3 +648,4 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 #include "emat_skygrid_host.hpp"
 #include "emat_exp_pop_host.hpp"
 #include "emat_subst_host.hpp"
+#include "emat_mpox_host.hpp"

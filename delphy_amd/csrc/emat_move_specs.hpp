@@ -1,7 +1,7 @@
 // emat_move_specs.hpp -- what a global-move spec must satisfy before any model is looked at: one function per spec, the text of the first fault or nullptr.
 //
-// No HIP in here: the backend's entry points (emat_skygrid_host.hpp, emat_exp_pop_host.hpp, emat_subst_host.hpp) and the run driver's setters (emat_run.cpp) both refuse
-// with these texts.  Also hky_derive_q, the q of an HKY model, which both derive.
+// No HIP in here: the backend's entry points (emat_skygrid_host.hpp, emat_exp_pop_host.hpp, emat_subst_host.hpp, emat_mpox_host.hpp) and the run driver's setters (emat_run.cpp) both refuse
+// with these texts.  Also what both derive alike: hky_derive_q, the q of an HKY model; mpox_derive_q and apobec_context_partition, the two q and the site partition of the APOBEC model.
 #ifndef EMAT_MOVE_SPECS_HPP_
 #define EMAT_MOVE_SPECS_HPP_
 
@@ -55,6 +55,39 @@ inline void hky_derive_q(double kappa, const double pi[4], double q[16]) {
   double rowv[4]; for (int b = 0; b < 4; ++b) { rowv[b] = 0.0; for (int a = 0; a < 4; ++a) rowv[b] += pi[a] * r[a][b]; }
   double R = 0.0; for (int b = 0; b < 4; ++b) R += rowv[b] * pi[b];
   for (int a = 0; a < 4; ++a) { q[a * 4 + a] = 0.0; for (int b = 0; b < 4; ++b) if (a != b) { q[a * 4 + b] = r[a][b] / R * pi[b]; q[a * 4 + a] -= q[a * 4 + b]; } }
+}
+
+// The APOBEC (mpox) model's moves (emat_mpox_host.hpp; the run driver's setter, which brings its own mu, passes with_model = false).
+constexpr int k_mpox_max_rounds = 4096;
+inline const char* mpox_spec_fault(const emat_mpox_spec& s, bool with_model = true) {
+  if (with_model && !finite_positive(s.mu)) return "mu must be finite and positive";
+  if (!(std::isfinite(s.mu_star) && s.mu_star >= 0.0)) return "mu_star must be finite and not negative";
+  if (!std::isfinite(s.mu_prior_alpha)) return "mu_prior_alpha must be finite";
+  if (!std::isfinite(s.mu_prior_beta)) return "mu_prior_beta must be finite";
+  if (s.rounds < 0) return "rounds must not be negative";
+  return nullptr;
+}
+
+// q of the APOBEC model's two site partitions (Run::derive_evo, reference run.cpp:407-432): Jukes-Cantor everywhere, and on the sites with
+// APOBEC context (partition 1) the extra rate 2 rho of TC>TT and of GA>AA.  Letters: A, C, G, T = 0 .. 3.  pi is 0.25 and mu the same in both.
+inline void mpox_derive_q(double rho, double q0[16], double q1[16]) {
+  for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) q0[a * 4 + b] = (a == b) ? -1.0 : 1. / 3.;
+  for (int k = 0; k < 16; ++k) q1[k] = q0[k];
+  q1[1 * 4 + 3] += 2 * rho; q1[1 * 4 + 1] -= 2 * rho;
+  q1[2 * 4 + 0] += 2 * rho; q1[2 * 4 + 2] -= 2 * rho;
+}
+
+// The site partition by APOBEC context of a sequence (Run::set_mpox_hack_enabled, reference run.cpp:370-382): site l is of partition 1 when
+// it follows a T and holds C (not yet mutated) or T (already mutated), or precedes an A and holds G or A.  Returns how many are.
+inline int apobec_context_partition(const uint8_t* seq, int L, int32_t* partition_for_site) {
+  int count = 0;
+  for (int l = 0; l != L; ++l) {
+    const bool apobec_context = ((l != 0) && (seq[l - 1] == 3) && ((seq[l] == 1) || (seq[l] == 3))) ||
+                                ((l + 1 != L) && (seq[l + 1] == 0) && ((seq[l] == 2) || (seq[l] == 0)));
+    if (apobec_context) ++count;
+    partition_for_site[l] = apobec_context ? 1 : 0;
+  }
+  return count;
 }
 
 }  // namespace emat

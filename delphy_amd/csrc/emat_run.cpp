@@ -54,6 +54,9 @@ struct RunDriver {
   bool skygrid_moves_on = false; emat_skygrid_spec sky_spec{}; uint64_t skygrid_rounds = 0;   // Run's Skygrid settings with skygrid_tau_, and how many rounds of the Skygrid moves have drawn a key
   bool exp_pop_moves_on = false; emat_exp_pop_spec xp_spec{}; uint64_t exp_pop_rounds = 0;      // Run's Exp_pop_model settings, and how many rounds of the Exponential moves have drawn a key
   bool subst_moves_on = false; emat_subst_spec sb_spec{}; uint64_t subst_rounds = 0;            // Run's mu prior and switches (the model is hky_* above), and how many rounds of the substitution-model moves have drawn a key
+  // The APOBEC (mpox) model (Run::set_mpox_hack_enabled, run.cpp:359-398): two site partitions cut by the APOBEC context of the sequence at node 0, mu and mu* of its own
+  // (hky_mu is handed over at enabling and handed back at disabling), Run's mu prior with its switch and the number of rounds, and how many rounds of its moves have drawn a key
+  bool mpox_on = false; emat_mpox_spec mx_spec{}; double mpox_mu = 0, mpox_mu_star = 0; std::vector<int32_t> mpox_partition_for_site; int mpox_context_sites = 0; uint64_t mpox_rounds = 0;
   double t_step = 1.0; bool t_step_set = false;
   int only_displacing_inner_nodes = 0, topology_moves_enabled = 1;
   bool reference_remainder = false;   // the remainder of count / parts goes to part 0 as in Run::run_local_moves (run.cpp:683-689), instead of one move per part
@@ -182,6 +185,7 @@ struct RunDriver {
   // ---- What goes to the backend.
   emat_status push_model() {
     if (!backend) return EMAT_OK;
+    if (mpox_on) return push_mpox_model();
     if (!have_hky) return fail(EMAT_ERR_STATE, "emat_run_set_hky must be called first");
     EMAT_TRY(bk(emat_set_ref_sequence(backend, ref.data(), L)));
     // Hky_model::derive_site_evo_model (evo_hky.cpp:7-50)
@@ -191,6 +195,17 @@ struct RunDriver {
     std::vector<int32_t> pfs(L, 0);
     std::vector<double> nu = nu_l.empty() ? std::vector<double>(L, 1.0) : nu_l;
     EMAT_TRY(bk(emat_set_evo(backend, 1, &hky_mu, pi, q, nu.data(), pfs.data())));
+    EMAT_TRY(bk(emat_set_flags(backend, tree.t_max_tip(), only_displacing_inner_nodes, topology_moves_enabled)));
+    model_went_out();
+    return EMAT_OK;
+  }
+  emat_status push_mpox_model() {   // push_model with the APOBEC model on: Run::derive_evo's other arm (run.cpp:405-432)
+    EMAT_TRY(bk(emat_set_ref_sequence(backend, ref.data(), L)));
+    const double mu[2] = {mpox_mu, mpox_mu}, pi[8] = {0.25, 0.25, 0.25, 0.25, 0.25, 0.25, 0.25, 0.25};
+    double q[32];
+    mpox_derive_q(mpox_mu_star / mpox_mu, q, q + 16);   // (emat_move_specs.hpp: the backend derives the same q after its moves)
+    std::vector<double> nu = nu_l.empty() ? std::vector<double>(L, 1.0) : nu_l;
+    EMAT_TRY(bk(emat_set_evo(backend, 2, mu, pi, q, nu.data(), mpox_partition_for_site.data())));
     EMAT_TRY(bk(emat_set_flags(backend, tree.t_max_tip(), only_displacing_inner_nodes, topology_moves_enabled)));
     model_went_out();
     return EMAT_OK;
@@ -420,7 +435,7 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // ---- The global moves: four groups (substitution model, site rates, Skygrid, Exponential population), one owner for each rule they share.
+  // ---- The global moves: five groups (substitution model or the APOBEC model, site rates, Skygrid, Exponential population), one owner for each rule they share.
   static constexpr const char* kShardedStatistics = "a sharded run gathers the part lengths and sums S, R across ranks itself (see emat_backend.h)";
   static constexpr uint64_t kSiteRateKeyTag = 0x5349544552415445ull;   // "SITERATE"
   // One round of a group: the key from the group's counter under its tag, the caller's trace buffer handed through, the counter bumped only when the backend did the round.
@@ -456,6 +471,7 @@ struct RunDriver {
   // there, which never leave it (emat_parts_subst_moves).  The accepted model becomes the run's: the backend holds it already, the next push sends it again.
   static constexpr uint64_t kSubstKeyTag = 0x5355425354303031ull;   // "SUBST001"
   emat_status subst_moves(emat_subst_result* out) {
+    EMAT_TRY(mpox_bars_subst_moves());
     EMAT_TRY(need_backend());
     EMAT_TRY(need_parts_out());
     if (!tree_cut) return fail(EMAT_ERR_STATE, "the substitution-model moves read the parts: repartition first");
@@ -465,6 +481,60 @@ struct RunDriver {
     emat_subst_result res{};
     EMAT_TRY(keyed_round(subst_rounds, kSubstKeyTag, out, res, [&](uint64_t key) { return emat_parts_subst_moves(backend, &spec, key, &res); }));
     hky_mu = res.mu; hky_kappa = res.kappa; for (int a = 0; a < 4; ++a) hky_pi[a] = res.pi[a];
+    if (out) *out = res;
+    return EMAT_OK;
+  }
+
+  // ---- The APOBEC (mpox) model: Run::set_mpox_hack_enabled (run.cpp:359-398) and Run::mpox_hack_moves (:823-951).
+  static constexpr uint64_t kMpoxKeyTag = 0x4D504F584D4F5631ull;   // "MPOXMOV1"
+  // The model's mu IS the run's mu, and the substitution-model moves would draw it a second time and install an HKY q: the two groups are the two arms of
+  // one branch (run.cpp:703-719).  Both directions of the exclusion are decided here.
+  emat_status mpox_bars_subst_moves() { return mpox_on ? fail(EMAT_ERR_STATE, "the APOBEC model is on (emat_run_set_mpox): its moves take the place of the substitution-model moves") : EMAT_OK; }
+  emat_status set_mpox(int32_t on, const emat_mpox_spec* spec) {
+    const std::string w = "emat_run_set_mpox: ";
+    if (!on) {   // :389-396
+      if (!mpox_on) return EMAT_OK;
+      mpox_on = false; mpox_partition_for_site.clear(); mpox_context_sites = 0;
+      hky_mu = mpox_mu;
+      model_changed();
+      return EMAT_OK;
+    }
+    if (!spec) return fail(EMAT_ERR_INVALID_ARGUMENT, w + "spec must not be null");
+    if (const char* why = mpox_spec_fault(*spec, false)) return fail(EMAT_ERR_INVALID_ARGUMENT, w + why);
+    if (spec->rounds > k_mpox_max_rounds) return fail(EMAT_ERR_INVALID_ARGUMENT, w + "rounds must not exceed 4096");
+    if (subst_moves_on) return fail(EMAT_ERR_STATE, w + "the substitution-model moves are on (emat_run_set_subst_moves): the APOBEC model's moves take their place");
+    if (mpox_on) { const double mu_star = mx_spec.mu_star; mx_spec = *spec; mx_spec.mu_star = mu_star; return EMAT_OK; }   // already on (:360): the switches alone; the partition, mu and mu* stay
+    if (!have_hky) return fail(EMAT_ERR_STATE, w + "emat_run_set_hky must be called first");
+    if (!finite_positive(hky_mu)) return fail(EMAT_ERR_INVALID_ARGUMENT, w + "the run's mu must be finite and positive");
+    if (tree_cut) return fail(EMAT_ERR_STATE, w + "the sequence at node 0 is read from the assembled tree: reassemble first");
+    EMAT_TRY(ensure_host_tree());
+    if (tree.nodes.empty() || !tree.nodes[0].is_tip()) return fail(EMAT_ERR_STATE, w + "node 0 of the tree is not a tip");   // :365-366
+    // view_of_sequence_at(tree_, 0) (phylo_tree_calc.cpp:19-35): the reference sequence with the mutations from the root down to node 0 applied in order
+    std::vector<int32_t> path;
+    for (int32_t v = 0; v != EMAT_NO_NODE; v = tree.nodes[(size_t)v].parent) { path.push_back(v); if (path.size() > tree.nodes.size()) return fail(EMAT_ERR_INTERNAL, w + "the tree has a cycle"); }
+    std::vector<uint8_t> seq = ref;
+    for (size_t k = path.size(); k-- > 0;) for (const HMut& m : tree.nodes[(size_t)path[k]].muts) if (m.site >= 0 && m.site < L) seq[(size_t)m.site] = m.to;
+    mpox_partition_for_site.assign((size_t)L, 0);
+    mpox_context_sites = apobec_context_partition(seq.data(), L, mpox_partition_for_site.data());   // :369-382
+    mx_spec = *spec;
+    mpox_mu = hky_mu; mpox_mu_star = spec->mu_star;   // :387-388 (the reference starts mu* at 0)
+    mpox_on = true;
+    model_changed();
+    return EMAT_OK;
+  }
+  // `rounds` rounds of the Gibbs draws of mu and rho on the device, from the statistics of the parts out there, which never leave it (emat_parts_mpox_moves).
+  // The new mu and mu* become the run's: the backend holds the model already, the next push sends it again.
+  emat_status mpox_moves(emat_mpox_result* out) {
+    EMAT_TRY(need_backend());
+    if (!mpox_on) return fail(EMAT_ERR_STATE, "the APOBEC model is off: emat_run_set_mpox first");
+    EMAT_TRY(need_parts_out());
+    if (!tree_cut) return fail(EMAT_ERR_STATE, "the APOBEC model's moves read the parts: repartition first");
+    if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
+    emat_mpox_spec spec = mx_spec;
+    spec.mu = mpox_mu; spec.mu_star = mpox_mu_star;
+    emat_mpox_result res{};
+    EMAT_TRY(keyed_round(mpox_rounds, kMpoxKeyTag, out, res, [&](uint64_t key) { return emat_parts_mpox_moves(backend, &spec, key, &res); }));
+    mpox_mu = res.mu; mpox_mu_star = res.mu_star;
     if (out) *out = res;
     return EMAT_OK;
   }
@@ -545,6 +615,7 @@ struct RunDriver {
       EMAT_TRY(repartition());
       laps.lap(); laps.mark("cycle: 1 repartition");
       if (subst_moves_on) EMAT_TRY(subst_moves(nullptr));           // groups 1 and 2 of run_global_moves, before the site rates as there (run.cpp:703-732)
+      if (mpox_on) EMAT_TRY(mpox_moves(nullptr));                   // ... or their other arm, the APOBEC model's (:717-719)
       if (site_rate_moves_on) EMAT_TRY(site_rate_moves(nullptr));   // where the reference runs its global moves (run.cpp:635-641)
       const int64_t k = std::min(per_cycle, steps - done);
       EMAT_TRY(run_moves(k));
@@ -857,6 +928,7 @@ emat_status emat_run_get_exp_pop(emat_run* r, double* n0, double* g) {
   return EMAT_OK;
 }
 emat_status emat_run_set_subst_moves(emat_run* r, int32_t on, const emat_subst_spec* spec) {   // (mu, kappa and pi of the spec are ignored: the run's own are used)
+  if (r && on) EMAT_TRY(r->d.mpox_bars_subst_moves());
   return set_moves_spec(r, "emat_run_set_subst_moves: ", on, spec, [](const emat_subst_spec& s) { return s.rounds > k_subst_max_rounds ? "rounds must not exceed 4096" : subst_spec_fault(s, false); }, &RunDriver::subst_moves_on, &RunDriver::sb_spec);
 }
 emat_status emat_run_subst_moves(emat_run* r, emat_subst_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.subst_moves(out); }
@@ -866,6 +938,25 @@ emat_status emat_run_get_hky(emat_run* r, double* mu, double* kappa, double* pi)
   if (mu) *mu = r->d.hky_mu;
   if (kappa) *kappa = r->d.hky_kappa;
   if (pi) std::copy(r->d.hky_pi, r->d.hky_pi + 4, pi);
+  return EMAT_OK;
+}
+emat_status emat_run_set_mpox(emat_run* r, int32_t on, const emat_mpox_spec* spec) {   // (mu of the spec is ignored: the run's own is used)
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  try { return r->d.set_mpox(on, spec); } catch (const std::exception& ex) { return r->d.fail(EMAT_ERR_INTERNAL, ex.what()); }
+}
+emat_status emat_run_mpox_moves(emat_run* r, emat_mpox_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.mpox_moves(out); }
+emat_status emat_run_get_mpox(emat_run* r, double* mu, double* mu_star) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!r->d.mpox_on) return r->d.fail(EMAT_ERR_STATE, "emat_run_get_mpox: the APOBEC model is off");
+  if (mu) *mu = r->d.mpox_mu;
+  if (mu_star) *mu_star = r->d.mpox_mu_star;
+  return EMAT_OK;
+}
+emat_status emat_run_get_mpox_partition(emat_run* r, int32_t* partition_for_site, int32_t* count) {
+  if (!r) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!r->d.mpox_on) return r->d.fail(EMAT_ERR_STATE, "emat_run_get_mpox_partition: the APOBEC model is off");
+  if (partition_for_site) std::copy(r->d.mpox_partition_for_site.begin(), r->d.mpox_partition_for_site.end(), partition_for_site);
+  if (count) *count = r->d.mpox_context_sites;
   return EMAT_OK;
 }
 emat_status emat_run_get_site_rates(emat_run* r, double* alpha, double* nu_l) {

@@ -181,6 +181,12 @@ struct SubstScratch {
   DevBuf<emat_subst_step> trace;
 };
 
+// What the APOBEC model's moves work in (emat_mpox_kernels.hpp, emat_mpox_host.hpp) beside the statistics record above: the result, the trace; grow-only.
+struct MpoxScratch {
+  DevBuf<double> result;
+  DevBuf<emat_mpox_round> trace;
+};
+
 // What the site-rate moves work in (emat_site_rate_kernels.hpp, emat_site_rate_host.hpp): grow-only, sized by the handle's L at the first call.
 struct SiteRateScratch {
   DevBuf<double> T, nu_new, d_log_G, d_prior, result; DevBuf<int32_t> M;
@@ -322,6 +328,7 @@ struct emat_backend {
   ExpPopScratch xp;                 // what emat_exp_pop_moves works in
   SiteRateScratch sr;               // what emat_site_rate_moves works in
   SubstScratch sb;                  // what emat_subst_moves works in
+  MpoxScratch mx;                   // what emat_mpox_moves works in (the statistics record is sb.stats)
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
   int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs

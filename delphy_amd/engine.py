@@ -329,6 +329,69 @@ def _subst_result(res: "_SubstResultC", trace) -> "SubstMovesResult":
     return r
 
 
+class _MpoxSpecC(C.Structure):
+    _fields_ = [("mu", C.c_double), ("mu_star", C.c_double), ("mu_prior_alpha", C.c_double), ("mu_prior_beta", C.c_double), ("do_mu", C.c_int32), ("rounds", C.c_int32)]
+
+
+_MPOX_ROUND_DOUBLES = ("mu", "rho", "Ttwiddle_eff", "mu_shape", "mu_rate", "mu_draw", "mu_delta_log_G", "mu_delta_log_other_priors",
+                       "alpha", "beta", "Q_lo", "Q_hi", "u", "rand_Q", "y", "k", "new_rho", "rho_delta_log_G")
+_MPOX_ROUND_INTS = ("mu_done", "rho_done", "rho_degenerate", "reserved")
+
+
+class _MpoxRoundC(C.Structure):
+    _fields_ = [(f, C.c_double) for f in _MPOX_ROUND_DOUBLES] + [(f, C.c_int32) for f in _MPOX_ROUND_INTS]
+
+
+class _MpoxResultC(C.Structure):
+    _fields_ = [("mu", C.c_double), ("mu_star", C.c_double), ("M", C.c_double), ("M_star", C.c_double), ("Ttwiddle", C.c_double), ("Ttwiddle_star", C.c_double),
+                ("delta_log_G", C.c_double), ("delta_log_other_priors", C.c_double), ("rho_skipped", C.c_int32), ("rho_degenerate", C.c_int32),
+                ("trace", C.POINTER(_MpoxRoundC)), ("trace_capacity", C.c_int32)]
+
+
+MPOX_ROUND_DTYPE = np.dtype([(f, "f8") for f in _MPOX_ROUND_DOUBLES] + [(f, "i4") for f in _MPOX_ROUND_INTS])
+_MPOX_TRACE = (_MpoxResultC, _MpoxRoundC, MPOX_ROUND_DTYPE)   # ... and one of the APOBEC model's moves (steps = rounds)
+
+
+@dataclass
+class MpoxSpec:
+    """The settings of the APOBEC (mpox) model's moves (include/emat_backend.h: emat_mpox_spec) with the mu and mu* they start from; the defaults of
+    the prior, the switch and the rounds are the reference's."""
+    mu: float = 1e-3
+    mu_star: float = 0.0
+    mu_prior_alpha: float = 1.0
+    mu_prior_beta: float = 0.0
+    do_mu: bool = True
+    rounds: int = 10
+
+    def c_struct(self) -> "_MpoxSpecC":
+        return _MpoxSpecC(float(self.mu), float(self.mu_star), float(self.mu_prior_alpha), float(self.mu_prior_beta), int(self.do_mu), int(self.rounds))
+
+
+@dataclass
+class MpoxMovesResult:
+    """What emat_mpox_moves returns (include/emat_backend.h: emat_mpox_result)."""
+    mu: float
+    mu_star: float
+    M: float
+    M_star: float
+    Ttwiddle: float
+    Ttwiddle_star: float
+    delta_log_G: float
+    delta_log_other_priors: float
+    rho_skipped: int
+    rho_degenerate: int
+    trace: Optional[np.ndarray]    # [rounds] records of MPOX_ROUND_DTYPE, or None when not asked for
+
+
+def mpox_q_matrices(rho: float):
+    """(q0, q1) [4][4] of the APOBEC model at rho = mu* / mu: Run::derive_evo (reference run.cpp:407-432), as mpox_derive_q (csrc/emat_move_specs.hpp) spells it."""
+    q0 = np.full((4, 4), 1.0 / 3.0); np.fill_diagonal(q0, -1.0)
+    q1 = q0.copy()
+    q1[1, 3] += 2 * rho; q1[1, 1] -= 2 * rho
+    q1[2, 0] += 2 * rho; q1[2, 2] -= 2 * rho
+    return q0, q1
+
+
 @dataclass
 class SamplesProbe:
     """What emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors return (include/emat_backend.h: emat_samples_probe_result).
@@ -617,6 +680,8 @@ def load_library():
         "emat_tree_exp_pop_moves": [B, P(_PopModelC), P(_ExpPopSpecC), dbl, dbl, u64, P(_ExpPopResultC)],
         "emat_subst_moves": [B, P(_SubstSpecC), i32, P(dbl), P(i64), P(i64), u64, P(_SubstResultC)], "emat_parts_subst_stats": [B, P(dbl), P(i64), P(i64)],
         "emat_parts_subst_moves": [B, P(_SubstSpecC), u64, P(_SubstResultC)], "emat_get_evo": [B, P(i32), P(dbl), P(dbl), P(dbl)],
+        "emat_mpox_moves": [B, P(_MpoxSpecC), P(dbl), P(i64), u64, P(_MpoxResultC)], "emat_parts_mpox_moves": [B, P(_MpoxSpecC), u64, P(_MpoxResultC)],
+        "emat_run_set_mpox": [R, i32, P(_MpoxSpecC)], "emat_run_mpox_moves": [R, P(_MpoxResultC)], "emat_run_get_mpox": [R, P(dbl), P(dbl)], "emat_run_get_mpox_partition": [R, P(i32), P(i32)],
         "emat_run_set_subst_moves": [R, i32, P(_SubstSpecC)], "emat_run_subst_moves": [R, P(_SubstResultC)], "emat_run_get_hky": [R, P(dbl), P(dbl), P(dbl)],
         "emat_run_set_exp_pop_moves": [R, i32, P(_ExpPopSpecC)], "emat_run_exp_pop_moves": [R, P(_ExpPopResultC)], "emat_run_get_exp_pop": [R, P(dbl), P(dbl)],
         "emat_run_set_skygrid_moves": [R, i32, P(_SkygridSpecC)], "emat_run_skygrid_moves": [R, P(_SkygridResultC)], "emat_run_get_skygrid": [R, P(dbl), P(dbl)],
@@ -1366,6 +1431,25 @@ class EmatBackend:
         self._ck(self._lib.emat_parts_subst_moves(self._h, C.byref(sp), int(key) & _KEY_MASK, C.byref(res)), "emat_parts_subst_moves")
         return _subst_result(res, tr)
 
+    def mpox_moves(self, spec: "MpoxSpec", Ttwiddle_beta_a, num_muts_beta_ab, key: int = 0, trace: bool = False) -> "MpoxMovesResult":
+        """`spec.rounds` rounds of the Gibbs draws of mu and rho = mu* / mu of the APOBEC model on the device (include/emat_backend.h: emat_mpox_moves), from the
+        run's summed statistics of its two site partitions: Ttwiddle_beta_a [2][4] and num_muts_beta_ab [2][4][4]."""
+        T = np.ascontiguousarray(Ttwiddle_beta_a, np.float64); M = np.ascontiguousarray(num_muts_beta_ab, np.int64)
+        if T.size != 8 or M.size != 32:
+            raise ValueError("Ttwiddle_beta_a must be [2][4] and num_muts_beta_ab [2][4][4]")
+        sp = spec.c_struct()
+        res, tr = _traced_result_c(*_MPOX_TRACE, spec.rounds, trace)
+        self._ck(self._lib.emat_mpox_moves(self._h, C.byref(sp), T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int64)), int(key) & _KEY_MASK, C.byref(res)),
+                 "emat_mpox_moves")
+        return _traced_result(MpoxMovesResult, res, tr)
+
+    def parts_mpox_moves(self, spec: "MpoxSpec", key: int = 0, trace: bool = False) -> "MpoxMovesResult":
+        """emat_mpox_moves on the statistics of the parts on this handle, which never leave it (emat_parts_mpox_moves)."""
+        sp = spec.c_struct()
+        res, tr = _traced_result_c(*_MPOX_TRACE, spec.rounds, trace)
+        self._ck(self._lib.emat_parts_mpox_moves(self._h, C.byref(sp), int(key) & _KEY_MASK, C.byref(res)), "emat_parts_mpox_moves")
+        return _traced_result(MpoxMovesResult, res, tr)
+
     def get_evo(self):
         """(mu [P], pi [P][4], q [P][4][4]) of the model the handle holds (emat_get_evo)."""
         n = C.c_int32(0); dp = C.POINTER(C.c_double)
@@ -1663,6 +1747,32 @@ class EmatRun:
         res, tr = _traced_result_c(*_SUBST_TRACE, 2 * getattr(self, "_sb_rounds", 0), trace)
         self._ck(self._lib.emat_run_subst_moves(self._h, C.byref(res)), "emat_run_subst_moves")
         return _subst_result(res, tr)
+
+    def set_mpox(self, on: bool = True, spec: "MpoxSpec" = None):
+        """The APOBEC (mpox) model (emat_run_set_mpox): two site partitions cut by the APOBEC context of the sequence at node 0, and its moves once per cycle of
+        do_mcmc_steps where the substitution-model moves run; `spec`: mu* to start from, Run's mu prior, its switch and the rounds (its mu is ignored: the run's
+        own is used).  Off: one partition and the HKY model again."""
+        sp = (spec or MpoxSpec()).c_struct()
+        self._ck(self._lib.emat_run_set_mpox(self._h, 1 if on else 0, C.byref(sp)), "emat_run_set_mpox")
+        self._mx_rounds = int(sp.rounds)
+
+    def mpox_moves(self, trace: bool = False) -> "MpoxMovesResult":
+        """One call of the APOBEC model's moves while the parts are out (emat_run_mpox_moves): `rounds` times the mu draw and the rho draw."""
+        res, tr = _traced_result_c(*_MPOX_TRACE, getattr(self, "_mx_rounds", 0), trace)
+        self._ck(self._lib.emat_run_mpox_moves(self._h, C.byref(res)), "emat_run_mpox_moves")
+        return _traced_result(MpoxMovesResult, res, tr)
+
+    def mpox(self):
+        """(mu, mu*) of the APOBEC model as the driver holds them."""
+        mu, mu_star = C.c_double(), C.c_double()
+        self._ck(self._lib.emat_run_get_mpox(self._h, C.byref(mu), C.byref(mu_star)), "emat_run_get_mpox")
+        return mu.value, mu_star.value
+
+    def mpox_partition(self):
+        """(partition_for_site [L], the number of sites with APOBEC context) as drawn when the model was turned on."""
+        pfs = np.zeros(self.num_sites, np.int32); n = C.c_int32()
+        self._ck(self._lib.emat_run_get_mpox_partition(self._h, pfs.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "emat_run_get_mpox_partition")
+        return pfs, n.value
 
     def hky(self):
         """(mu, kappa, pi [4]) as the driver holds them."""

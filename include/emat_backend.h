@@ -835,6 +835,76 @@ emat_status emat_parts_subst_stats(emat_backend* h, double* Ttwiddle_beta_a /*[P
 emat_status emat_parts_subst_moves(emat_backend* h, const emat_subst_spec* spec, uint64_t key, emat_subst_result* out);
 emat_status emat_get_evo(emat_backend* h, int32_t* num_partitions, double* mu /*[P]*/, double* pi /*[P][4]*/, double* q /*[P][4][4]*/);
 
+/* ---- the APOBEC (mpox) model's moves: Gibbs rounds of mu and rho = mu* / mu ------------------------------------------------------
+ * replaces: the other arm of group 1 of Run::run_global_moves (reference run.cpp:703-719): Run::mpox_hack_moves (:823-951), on the device
+ * (csrc/emat_mpox_kernels.hpp) in ONE launch of one wavefront.  The model has two site partitions (Run::set_mpox_hack_enabled, :359-398):
+ * 0 = sites without APOBEC context, 1 = sites with it; Jukes-Cantor rates everywhere and on partition 1 the extra rate 2 rho of TC>TT and
+ * GA>AA (Run::derive_evo, :400-435; mpox_derive_q of csrc/emat_move_specs.hpp); pi = 0.25 and the same mu in both.
+ *
+ * Inputs are the statistics of the WHOLE run as emat_get_global_stats hands them out, for the 2 partitions.  From them (:854-905):
+ *   M = the sum of the counts off the diagonal       M* = M[1][C][T] + M[1][G][A]
+ *   Ttwiddle = the sum of all eight Ttwiddle_beta_a, beta outer and a inner       Ttwiddle* = T[1][C] + T[1][G]
+ * Round i = 0 .. rounds - 1 (:908-947):
+ *   rho = mu* / mu and Ttwiddle_eff = Ttwiddle + 2 rho Ttwiddle*, at the top of the round
+ *   mu draw (when do_mu)   mu ~ Gamma(shape = M + mu_prior_alpha - 1, rate = Ttwiddle_eff + mu_prior_beta), the sampler of
+ *                          emat_debug_sample_gamma; delta log G = -(new - old) Ttwiddle_eff + M log(new / old), the other priors grow by
+ *                          (alpha - 1) log(new / old) - beta (new - old) (:924-926)
+ *   rho draw (when Ttwiddle* > 0; else counted in rho_skipped)   k = 1 + 6 rho from Gamma(alpha = M* + 1, beta = mu Ttwiddle* / 3), with
+ *                          the NEW mu, truncated to [1, inf) by inverse transform (safe_sample_truncated_gamma, safe_gamma_math.h:110-139):
+ *                          Q_hi = Q(alpha, beta), Q_lo = 0, rand_Q = Q_lo + (Q_hi - Q_lo) u with u in (0, 1], y = Q^-1(alpha, rand_Q),
+ *                          k = max(1, y / beta), new_rho = (k - 1) / 6, mu* = mu new_rho;
+ *                          delta log G = -2 mu (new_rho - rho) Ttwiddle* + M* log((1 + 6 new_rho) / (1 + 6 rho)), rho the value from the
+ *                          top of the round (:939-944).  Where the reference aborts because Q_lo >= Q_hi (Q(alpha, beta) underflows), the
+ *                          step ends with rho and mu* unchanged and is counted in rho_degenerate.
+ * Q and its inverse are the device's incomplete-gamma routines (emat_debug_gamma), held to 1e-12 + 1e-10 Q and 1e-9 max(1, y) for
+ * alpha <= 1 000 and beta <= 1e5.  Every lane of the wavefront runs the same scalar arithmetic; no atomics: the same arguments give the
+ * same result BIT FOR BIT on every handle and in every call.
+ *
+ * Random numbers: the (key, id) streams of the site-rate moves under the next two pseudo-ids below the substitution-model moves':
+ *   0xFFFFFFF6  round i's mu draw starts at the stream's 64-bit word 256 i (a draw takes at most 193); drawn also when do_mu is 0,
+ *               provided shape and rate are positive
+ *   0xFFFFFFF5  round i's rho uniform is word i, in (0, 1]
+ * A round's draws depend on (key, i) alone.
+ *
+ * The call first finishes a pending pass.  Afterwards the handle's model is the new one, as if given to emat_set_evo: mu on both
+ * partitions, pi = 0.25, q0 and q1 = mpox_derive_q(mu* / mu) made on the host; nu_l, the site partitions and the reference sequence are
+ * untouched and nothing L-long is uploaded.
+ *
+ *   emat_parts_mpox_moves   emat_mpox_moves on the statistics of the parts on this handle (emat_parts_subst_stats' two arrays; the root
+ *                           counts are not read) without their leaving HBM: bit for bit what emat_mpox_moves returns when fed them.
+ *
+ * EMAT_ERR_INVALID_ARGUMENT (text in emat_last_error naming the first offender), all answered before the device is asked for: a null
+ * pointer; mu not finite or <= 0; mu_star not finite or < 0; mu_prior_alpha or mu_prior_beta not finite; rounds < 0; a trace with
+ * trace_capacity < rounds; a model on the handle with other than 2 site partitions; a Ttwiddle that is negative or not finite; a negative
+ * count; shape <= 0 or rate <= 0 for the first round's mu draw while do_mu is set (a later round's: after the launch, the model untouched).
+ * EMAT_ERR_CAPACITY: rounds > 4 096.  EMAT_ERR_STATE: before emat_set_evo; for the parts call, with no parts out or no root part on this
+ * handle.  EMAT_ERR_NO_DEVICE: a handle without a device, after these checks.  After any refusal the model is untouched and the next call works. */
+typedef struct emat_mpox_spec {
+  double mu, mu_star;                        /* the model the rounds start from (Run::mpox_mu_, mpox_mu_star_) */
+  double mu_prior_alpha, mu_prior_beta;      /* reference run.h:47-50; defaults 1 and 0 */
+  int32_t do_mu;                             /* Run::mu_move_enabled_ (:915) */
+  int32_t rounds;                            /* 10 in the reference (:908) */
+} emat_mpox_spec;
+typedef struct emat_mpox_round {
+  double mu, rho, Ttwiddle_eff;              /* held before the round; :911-912 */
+  double mu_shape, mu_rate, mu_draw;         /* :916-921; the draw is NaN when do_mu is 0 and shape or rate is not positive */
+  double mu_delta_log_G, mu_delta_log_other_priors;   /* :924-926; 0 when do_mu is 0 */
+  double alpha, beta, Q_lo, Q_hi, u, rand_Q, y, k, new_rho;   /* the rho draw (safe_gamma_math.h:117-138, run.cpp:940); 0 when skipped, from y on 0 when degenerate */
+  double rho_delta_log_G;                    /* :943-944 */
+  int32_t mu_done, rho_done, rho_degenerate, reserved;
+} emat_mpox_round;
+typedef struct emat_mpox_result {
+  double mu, mu_star;                        /* after the call */
+  double M, M_star, Ttwiddle, Ttwiddle_star; /* :863-866, :897-905 */
+  double delta_log_G, delta_log_other_priors;          /* of every draw */
+  int32_t rho_skipped, rho_degenerate;       /* rounds whose rho step did not run (Ttwiddle* = 0) / ended on Q_lo >= Q_hi */
+  emat_mpox_round* trace;                    /* may be NULL: room for `rounds` records, round i at [i] */
+  int32_t trace_capacity;                    /* in: records `trace` has room for (>= rounds) */
+} emat_mpox_result;
+emat_status emat_mpox_moves(emat_backend* h, const emat_mpox_spec* spec, const double* Ttwiddle_beta_a /*[2][4]*/, const int64_t* num_muts_beta_ab /*[2][4][4]*/,
+                            uint64_t key, emat_mpox_result* out);
+emat_status emat_parts_mpox_moves(emat_backend* h, const emat_mpox_spec* spec, uint64_t key, emat_mpox_result* out);
+
 /* replaces: Run::calc_cur_log_coalescent_prior (reference run.cpp:455-465), i.e. Scalable_coalescent_prior::calc_log_prior
  * (scalable_coalescent.cpp:163-187) with every node displaced to its current time (:88-138): the whole-tree grid prior
  *   - sum_cells t_step kbar (kbar - 1) / (2 Nbar)  -  sum over inner nodes of log N(t),

@@ -15,6 +15,7 @@
  *   Run::alpha_moves, gibbs_sample_all_nus                 emat_run_site_rate_moves  -> emat_site_rate_moves of the backend
  *     (run.cpp:1105-1235)
  *   Run::mu_move, hky_frequencies_move, hky_kappa_move     emat_run_subst_moves      -> emat_parts_subst_moves of the backend
+ *   Run::set_mpox_hack_enabled, mpox_hack_moves            emat_run_set_mpox, emat_run_mpox_moves -> emat_parts_mpox_moves of the backend
  *     (run.cpp:781-821, :953-1103)
  *
  * Also exports the seeded synthetic-EMAT generator used by the bench and the tests
@@ -271,6 +272,32 @@ emat_status emat_run_get_exp_pop(emat_run* r, double* n0, double* g /* either ma
 emat_status emat_run_set_subst_moves(emat_run* r, int32_t on, const emat_subst_spec* spec);
 emat_status emat_run_subst_moves(emat_run* r, emat_subst_result* out /* may be NULL */);   /* needs the parts out */
 emat_status emat_run_get_hky(emat_run* r, double* mu, double* kappa, double* pi /*[4]; any may be NULL */);
+
+/* The APOBEC (mpox) model of a run (Run::set_mpox_hack_enabled, reference run.cpp:359-398; Run::derive_evo's second arm, :405-432;
+ * Run::mpox_hack_moves, :823-951; emat_parts_mpox_moves of emat_backend.h).  Off by default: a run without it is what it was.
+ *   emat_run_set_mpox            on: the sites are cut into two partitions by the APOBEC context (:370-382) of the sequence at node 0 of the
+ *                                run's tree -- the reference sequence with the mutations on the path from the root down to node 0 applied
+ *                                in order, missations ignored, as view_of_sequence_at does; host work, once per run (a tree resident in HBM
+ *                                is brought to the host for it).  mu starts at the run's HKY mu and mu* at spec->mu_star (the reference: 0);
+ *                                do_mu, rounds (10 in the reference) and the mu prior are the group's switches; mu of the spec is ignored.
+ *                                From then on emat_run_push_params sends two partitions with mpox_derive_q(mu* / mu), and the run's kappa
+ *                                and pi rest.  On a run that has the model on already only the switches are taken.  EMAT_ERR_STATE: node 0
+ *                                is not a tip; the parts are out (reassemble first); no emat_run_set_hky yet; the substitution-model moves
+ *                                are on -- and emat_run_set_subst_moves(on) and emat_run_subst_moves are refused likewise while the model is
+ *                                on: the two groups are the two arms of one branch (:703-719).  EMAT_ERR_INVALID_ARGUMENT: what
+ *                                emat_mpox_moves refuses in the rest of a spec, more rounds than it holds, or a run's mu that is not positive.
+ *                                off (spec may be NULL): one partition again, and mu goes back to the HKY model (:391-395).
+ *   emat_run_mpox_moves          one call while the parts are out, like emat_run_subst_moves: the statistics of the parts never leave the
+ *                                device; the key of call k is the first word of Philox(counter k, key = run seed ^ a fixed tag of its own).
+ *                                The new mu and mu* become the run's.  `out` (may be NULL): out->trace may be NULL.  A sharded run is
+ *                                refused as the site-rate moves refuse it.
+ *   emat_run_get_mpox            mu and mu* as the run holds them (either may be NULL); EMAT_ERR_STATE with the model off.
+ *   emat_run_get_mpox_partition  the partition drawn at enabling and how many sites have APOBEC context (either may be NULL).
+ * With the model on, emat_run_do_mcmc_steps makes one call per cycle where it makes the substitution-model moves' call. */
+emat_status emat_run_set_mpox(emat_run* r, int32_t on, const emat_mpox_spec* spec);
+emat_status emat_run_mpox_moves(emat_run* r, emat_mpox_result* out /* may be NULL */);   /* needs the parts out */
+emat_status emat_run_get_mpox(emat_run* r, double* mu, double* mu_star);
+emat_status emat_run_get_mpox_partition(emat_run* r, int32_t* partition_for_site /*[L]*/, int32_t* count);
 
 /* [Skygrid or Exponential population moves when on] -> repartition -> [push params, substitution-model moves when on, site-rate moves
  * when on, local moves, reassemble] per cycle of `local_moves_per_cycle` moves (<= 0: 50 x nodes, the reference default
