@@ -150,8 +150,19 @@ emat_status emat_set_evo(emat_backend* h, int32_t P, const double* mu, const dou
   h->num_partitions = P;
   h->mu.assign(mu, mu + P); h->pi.assign(pi, pi + 4 * P); h->q.assign(q, q + 16 * P); h->nu_l.assign(nu_l, nu_l + h->L);
   h->have_evo = true;
-  refresh_ref_derived(h);
-  h->model_changed();   // Subrun::set_evo invalidates derived quantities (subrun.h:29-30)
+  install_model(h);
+  return EMAT_OK;
+}
+/* the model the handle holds (header: emat_get_evo) */
+emat_status emat_get_evo(emat_backend* h, int32_t* num_partitions, double* mu, double* pi, double* q) {
+  if (!h || !num_partitions) return EMAT_ERR_INVALID_ARGUMENT;
+  if (!h->have_evo) return fail(h, EMAT_ERR_STATE, "emat_set_evo must precede emat_get_evo");
+  const int P = h->num_partitions, room = *num_partitions;
+  *num_partitions = P;
+  if (room < P && (mu || pi || q)) return fail(h, EMAT_ERR_BUFFER_TOO_SMALL, "emat_get_evo: room for fewer site partitions than the model has");
+  if (mu) std::copy(h->mu.begin(), h->mu.end(), mu);
+  if (pi) std::copy(h->pi.begin(), h->pi.end(), pi);
+  if (q) std::copy(h->q.begin(), h->q.end(), q);
   return EMAT_OK;
 }
 emat_status emat_set_flags(emat_backend* h, double t_max_tip, int32_t only_displacing_inner_nodes, int32_t topology_moves_enabled) {
@@ -647,5 +658,6 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 #include "emat_coal_stats_host.hpp"
 #include "emat_skygrid_host.hpp"
 #include "emat_exp_pop_host.hpp"
+#include "emat_subst_stats_host.hpp"    // the parts' substitution statistics and the frame of the two groups that read them
 #include "emat_subst_host.hpp"
 #include "emat_mpox_host.hpp"

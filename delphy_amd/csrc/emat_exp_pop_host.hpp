@@ -22,7 +22,7 @@ emat_status xp_moves(emat_backend* h, const std::string& w, const emat_pop_model
   emat_status st = coal_check_origin(h, w, t_ref, t_step); if (st) return st;
   st = coal_check_host_values(h, w, t_ref, t_step, host); if (st) return st;
   st = host ? coal_check_capacity(h, w, host->first_cell, host->num_cells) : EMAT_OK; if (st) return st;
-  if (spec->rounds > k_xp_max_rounds) return fail(h, EMAT_ERR_CAPACITY, w + std::to_string(spec->rounds) + " rounds are more than the moves hold (" + std::to_string(k_xp_max_rounds) + ")");
+  if (spec->rounds > k_xp_max_rounds) return fail(h, EMAT_ERR_CAPACITY, w + rounds_beyond_text(spec->rounds, k_xp_max_rounds));
   HostLaps laps;   // (EMAT_VERBOSE=spans: the call by phase)
   st = coal_obtain(h, w, t_ref, t_step, host); if (st) return st;
   // the launch chain on the statistics in h->coal; everything in the handle's own buffers

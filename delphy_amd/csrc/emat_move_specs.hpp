@@ -6,6 +6,7 @@
 #define EMAT_MOVE_SPECS_HPP_
 
 #include <cmath>
+#include <string>
 #include "../../include/emat_backend.h"
 
 namespace emat {
@@ -31,8 +32,23 @@ inline const char* exp_pop_spec_fault(const emat_exp_pop_spec& s, const double* 
   return nullptr;
 }
 
+// THE sentence of a backend call asked for more rounds than its moves hold (EMAT_ERR_CAPACITY; the Exponential group's limit is its kernels' own, k_xp_max_rounds).
+inline std::string rounds_beyond_text(int rounds, int max_rounds) { return std::to_string(rounds) + " rounds are more than the moves hold (" + std::to_string(max_rounds) + ")"; }
+
+// The two groups that run as one wavefront, the substitution-model moves and the APOBEC model's: the rounds they hold, the run driver's setters' text for more, what their specs share.
+constexpr int k_one_wave_max_rounds = 4096;
+inline const char* rounds_limit_fault(int rounds) {
+  static const std::string text = "rounds must not exceed " + std::to_string(k_one_wave_max_rounds);
+  return rounds > k_one_wave_max_rounds ? text.c_str() : nullptr;
+}
+template <class Spec> inline const char* mu_prior_and_rounds_fault(const Spec& s) {
+  if (!std::isfinite(s.mu_prior_alpha)) return "mu_prior_alpha must be finite";
+  if (!std::isfinite(s.mu_prior_beta)) return "mu_prior_beta must be finite";
+  if (s.rounds < 0) return "rounds must not be negative";
+  return nullptr;
+}
+
 // The substitution-model moves (emat_subst_host.hpp; the run driver's setter, which brings its own model, passes with_model = false).
-constexpr int k_subst_max_rounds = 4096;
 inline const char* subst_spec_fault(const emat_subst_spec& s, bool with_model = true) {
   if (with_model) {
     if (!finite_positive(s.mu)) return "mu must be finite and positive";
@@ -41,10 +57,7 @@ inline const char* subst_spec_fault(const emat_subst_spec& s, bool with_model = 
     for (int a = 0; a < 4; ++a) { if (!(s.pi[a] > 0.0 && s.pi[a] < 1.0)) return "every pi[a] must lie inside (0, 1)"; sum += s.pi[a]; }
     if (!(std::fabs(sum - 1.0) <= 1e-9)) return "the pi[a] must add up to 1 within 1e-9";
   }
-  if (!std::isfinite(s.mu_prior_alpha)) return "mu_prior_alpha must be finite";
-  if (!std::isfinite(s.mu_prior_beta)) return "mu_prior_beta must be finite";
-  if (s.rounds < 0) return "rounds must not be negative";
-  return nullptr;
+  return mu_prior_and_rounds_fault(s);
 }
 
 // q of the HKY model (kappa, pi): Hky_model::derive_site_evo_model (reference evo_hky.cpp:7-50), statement for statement what the run
@@ -58,14 +71,10 @@ inline void hky_derive_q(double kappa, const double pi[4], double q[16]) {
 }
 
 // The APOBEC (mpox) model's moves (emat_mpox_host.hpp; the run driver's setter, which brings its own mu, passes with_model = false).
-constexpr int k_mpox_max_rounds = 4096;
 inline const char* mpox_spec_fault(const emat_mpox_spec& s, bool with_model = true) {
   if (with_model && !finite_positive(s.mu)) return "mu must be finite and positive";
   if (!(std::isfinite(s.mu_star) && s.mu_star >= 0.0)) return "mu_star must be finite and not negative";
-  if (!std::isfinite(s.mu_prior_alpha)) return "mu_prior_alpha must be finite";
-  if (!std::isfinite(s.mu_prior_beta)) return "mu_prior_beta must be finite";
-  if (s.rounds < 0) return "rounds must not be negative";
-  return nullptr;
+  return mu_prior_and_rounds_fault(s);
 }
 
 // q of the APOBEC model's two site partitions (Run::derive_evo, reference run.cpp:407-432): Jukes-Cantor everywhere, and on the sites with

@@ -71,6 +71,9 @@ void refresh_ref_derived(emat_backend* h) {
   for (int l = 0; l < L; ++l) ++h->ref_freqs[h->partition_for_site[l] * 4 + h->ref[l]];
   h->model_dirty = true;
 }
+// THE tail of every call that wrote a model into h->mu, pi, q or nu_l (emat_set_evo and the moves that draw one), by emat_set_evo's rules: what is derived from it
+// with the reference sequence follows, and what the slabs maintain belongs to the old one (Subrun::set_evo, subrun.h:29-30).  The site partitions and the sequence stay.
+void install_model(emat_backend* h) { refresh_ref_derived(h); h->model_changed(); }
 
 KernelArgs make_args(emat_backend* h) {
   KernelArgs a{};

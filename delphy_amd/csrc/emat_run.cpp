@@ -437,7 +437,20 @@ struct RunDriver {
 
   // ---- The global moves: five groups (substitution model or the APOBEC model, site rates, Skygrid, Exponential population), one owner for each rule they share.
   static constexpr const char* kShardedStatistics = "a sharded run gathers the part lengths and sums S, R across ranks itself (see emat_backend.h)";
-  static constexpr uint64_t kSiteRateKeyTag = 0x5349544552415445ull;   // "SITERATE"
+  // The five key tags (keyed_round).  A group that reads the parts out on the backend carries its tag with the noun of its texts, a population group with its own two and the model's kind.
+  struct PartsGroup { const char* moves; uint64_t tag; };
+  struct PopGroup { int32_t kind; const char* moves; const char* model; uint64_t tag; };
+  static constexpr uint64_t kSiteRateKeyTag = 0x5349544552415445ull;                                                  // "SITERATE"
+  static constexpr PartsGroup kSubstGroup{"the substitution-model moves", 0x5355425354303031ull};                   // "SUBST001"
+  static constexpr PartsGroup kMpoxGroup{"the APOBEC model's moves", 0x4D504F584D4F5631ull};                        // "MPOXMOV1"
+  static constexpr PopGroup kSkygridGroup{EMAT_POP_SKYGRID, "the Skygrid moves", "a Skygrid population model", 0x534B594752494431ull};                  // "SKYGRID1"
+  static constexpr PopGroup kExpPopGroup{EMAT_POP_EXP, "the Exponential population moves", "an exponential population model", 0x455850504F503031ull};   // "EXPPOP01"
+  // What a setter asks of its spec: there, and passing the backend's own checks (emat_move_specs.hpp), refused in its words behind the setter's name `w`.
+  template <class Spec, class Fault> emat_status check_moves_spec(const std::string& w, const Spec* spec, Fault fault) {
+    if (!spec) return fail(EMAT_ERR_INVALID_ARGUMENT, w + "spec must not be null");
+    if (const char* why = fault(*spec)) return fail(EMAT_ERR_INVALID_ARGUMENT, w + why);
+    return EMAT_OK;
+  }
   // One round of a group: the key from the group's counter under its tag, the caller's trace buffer handed through, the counter bumped only when the backend did the round.
   template <class Result, class Call> emat_status keyed_round(uint64_t& rounds, uint64_t tag, const Result* out, Result& res, Call&& call) {
     uint32_t w[4]; philox4x32_10_pure(rounds, seed ^ tag, w);
@@ -467,26 +480,30 @@ struct RunDriver {
     return EMAT_OK;
   }
 
-  // Run::mu_move, then sb_spec.rounds times hky_frequencies_move + hky_kappa_move (run.cpp:703-719), on the device from the statistics of the parts out
-  // there, which never leave it (emat_parts_subst_moves).  The accepted model becomes the run's: the backend holds it already, the next push sends it again.
-  static constexpr uint64_t kSubstKeyTag = 0x5355425354303031ull;   // "SUBST001"
-  emat_status subst_moves(emat_subst_result* out) {
-    EMAT_TRY(mpox_bars_subst_moves());
+  // One round of a group that runs on the device from the statistics of the parts out there, which never leave it: the preconditions, the backend's call, the tail.  The group's
+  // caller brings the spec with the run's model in it and takes the new model out of `res`: the backend holds it already, the next push sends it again.
+  template <class Spec, class Result, class OnParts>
+  emat_status parts_round(const PartsGroup& g, uint64_t& rounds, const Spec& spec, Result* out, Result& res, OnParts on_parts) {
     EMAT_TRY(need_backend());
     EMAT_TRY(need_parts_out());
-    if (!tree_cut) return fail(EMAT_ERR_STATE, "the substitution-model moves read the parts: repartition first");
+    if (!tree_cut) return fail(EMAT_ERR_STATE, std::string(g.moves) + " read the parts: repartition first");
     if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
+    EMAT_TRY(keyed_round(rounds, g.tag, out, res, [&](uint64_t key) { return on_parts(backend, &spec, key, &res); }));
+    if (out) *out = res;
+    return EMAT_OK;
+  }
+  // Run::mu_move, then sb_spec.rounds times hky_frequencies_move + hky_kappa_move (run.cpp:703-719): emat_parts_subst_moves.
+  emat_status subst_moves(emat_subst_result* out) {
+    EMAT_TRY(mpox_bars_subst_moves());
     emat_subst_spec spec = sb_spec;
     spec.mu = hky_mu; spec.kappa = hky_kappa; for (int a = 0; a < 4; ++a) spec.pi[a] = hky_pi[a];
     emat_subst_result res{};
-    EMAT_TRY(keyed_round(subst_rounds, kSubstKeyTag, out, res, [&](uint64_t key) { return emat_parts_subst_moves(backend, &spec, key, &res); }));
+    EMAT_TRY(parts_round(kSubstGroup, subst_rounds, spec, out, res, emat_parts_subst_moves));
     hky_mu = res.mu; hky_kappa = res.kappa; for (int a = 0; a < 4; ++a) hky_pi[a] = res.pi[a];
-    if (out) *out = res;
     return EMAT_OK;
   }
 
   // ---- The APOBEC (mpox) model: Run::set_mpox_hack_enabled (run.cpp:359-398) and Run::mpox_hack_moves (:823-951).
-  static constexpr uint64_t kMpoxKeyTag = 0x4D504F584D4F5631ull;   // "MPOXMOV1"
   // The model's mu IS the run's mu, and the substitution-model moves would draw it a second time and install an HKY q: the two groups are the two arms of
   // one branch (run.cpp:703-719).  Both directions of the exclusion are decided here.
   emat_status mpox_bars_subst_moves() { return mpox_on ? fail(EMAT_ERR_STATE, "the APOBEC model is on (emat_run_set_mpox): its moves take the place of the substitution-model moves") : EMAT_OK; }
@@ -499,9 +516,7 @@ struct RunDriver {
       model_changed();
       return EMAT_OK;
     }
-    if (!spec) return fail(EMAT_ERR_INVALID_ARGUMENT, w + "spec must not be null");
-    if (const char* why = mpox_spec_fault(*spec, false)) return fail(EMAT_ERR_INVALID_ARGUMENT, w + why);
-    if (spec->rounds > k_mpox_max_rounds) return fail(EMAT_ERR_INVALID_ARGUMENT, w + "rounds must not exceed 4096");
+    EMAT_TRY(check_moves_spec(w, spec, [](const emat_mpox_spec& s) { const char* why = mpox_spec_fault(s, false); return why ? why : rounds_limit_fault(s.rounds); }));
     if (subst_moves_on) return fail(EMAT_ERR_STATE, w + "the substitution-model moves are on (emat_run_set_subst_moves): the APOBEC model's moves take their place");
     if (mpox_on) { const double mu_star = mx_spec.mu_star; mx_spec = *spec; mx_spec.mu_star = mu_star; return EMAT_OK; }   // already on (:360): the switches alone; the partition, mu and mu* stay
     if (!have_hky) return fail(EMAT_ERR_STATE, w + "emat_run_set_hky must be called first");
@@ -522,28 +537,20 @@ struct RunDriver {
     model_changed();
     return EMAT_OK;
   }
-  // `rounds` rounds of the Gibbs draws of mu and rho on the device, from the statistics of the parts out there, which never leave it (emat_parts_mpox_moves).
-  // The new mu and mu* become the run's: the backend holds the model already, the next push sends it again.
+  // `rounds` rounds of the Gibbs draws of mu and rho: emat_parts_mpox_moves.
   emat_status mpox_moves(emat_mpox_result* out) {
-    EMAT_TRY(need_backend());
+    EMAT_TRY(need_backend());   // (asked here as well: a run without a backend is told so before it is told that the model is off)
     if (!mpox_on) return fail(EMAT_ERR_STATE, "the APOBEC model is off: emat_run_set_mpox first");
-    EMAT_TRY(need_parts_out());
-    if (!tree_cut) return fail(EMAT_ERR_STATE, "the APOBEC model's moves read the parts: repartition first");
-    if (shard_world > 1) return fail(EMAT_ERR_STATE, kShardedStatistics);
     emat_mpox_spec spec = mx_spec;
     spec.mu = mpox_mu; spec.mu_star = mpox_mu_star;
     emat_mpox_result res{};
-    EMAT_TRY(keyed_round(mpox_rounds, kMpoxKeyTag, out, res, [&](uint64_t key) { return emat_parts_mpox_moves(backend, &spec, key, &res); }));
+    EMAT_TRY(parts_round(kMpoxGroup, mpox_rounds, spec, out, res, emat_parts_mpox_moves));
     mpox_mu = res.mu; mpox_mu_star = res.mu_star;
-    if (out) *out = res;
     return EMAT_OK;
   }
 
   // The population moves (run.cpp:754-778) run on the device, on the ASSEMBLED tree, in one process, on a model of their own kind: from the tree in HBM
   // where it lives there, else from the two statistics made here from the host's tree (scalable_coalescent.cpp:88-138).
-  struct PopGroup { int32_t kind; const char* moves; const char* model; uint64_t tag; };
-  static constexpr PopGroup kSkygridGroup{EMAT_POP_SKYGRID, "the Skygrid moves", "a Skygrid population model", 0x534B594752494431ull};            // (the key's tag: "SKYGRID1")
-  static constexpr PopGroup kExpPopGroup{EMAT_POP_EXP, "the Exponential population moves", "an exponential population model", 0x455850504F503031ull};   // ("EXPPOP01")
   void host_tree_coalescent_stats(double t_ref, double ts, int32_t& first_cell, std::vector<double>& k_bar, std::vector<double>& inner_t) const {
     const auto cell = [&](double t) { return (int64_t)std::floor((t - t_ref) / ts); };
     double t_last = -INFINITY;
@@ -885,11 +892,10 @@ emat_status emat::RunDriver::get_Ttwiddle_l(double* Ttwiddle_l) {
   EMAT_TRY(d.bk(emat_Ttwiddle_l_partial(d.backend, off.data(), node.data(), val.data(), S.data(), R.data(), &T)));
   return d.bk(emat_Ttwiddle_l_finish(d.backend, S.data(), R.data(), T, Ttwiddle_l));
 }
-// A population group's setter: the spec must pass the backend's own checks (emat_move_specs.hpp), refused in its words behind the setter's name `w`.
+// A group's setter whose spec is all it keeps: checked (check_moves_spec), then the switch and the spec.
 template <class Spec, class Fault> emat_status set_moves_spec(emat_run* r, const std::string& w, int32_t on, const Spec* spec, Fault fault, bool emat::RunDriver::*is_on, Spec emat::RunDriver::*kept) {
   if (!r) return EMAT_ERR_INVALID_ARGUMENT;
-  if (!spec) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, w + "spec must not be null");
-  if (const char* why = fault(*spec)) return r->d.fail(EMAT_ERR_INVALID_ARGUMENT, w + why);
+  EMAT_TRY(r->d.check_moves_spec(w, spec, fault));
   r->d.*is_on = on != 0; r->d.*kept = *spec;
   return EMAT_OK;
 }
@@ -929,7 +935,7 @@ emat_status emat_run_get_exp_pop(emat_run* r, double* n0, double* g) {
 }
 emat_status emat_run_set_subst_moves(emat_run* r, int32_t on, const emat_subst_spec* spec) {   // (mu, kappa and pi of the spec are ignored: the run's own are used)
   if (r && on) EMAT_TRY(r->d.mpox_bars_subst_moves());
-  return set_moves_spec(r, "emat_run_set_subst_moves: ", on, spec, [](const emat_subst_spec& s) { return s.rounds > k_subst_max_rounds ? "rounds must not exceed 4096" : subst_spec_fault(s, false); }, &RunDriver::subst_moves_on, &RunDriver::sb_spec);
+  return set_moves_spec(r, "emat_run_set_subst_moves: ", on, spec, [](const emat_subst_spec& s) { const char* why = rounds_limit_fault(s.rounds); return why ? why : subst_spec_fault(s, false); }, &RunDriver::subst_moves_on, &RunDriver::sb_spec);
 }
 emat_status emat_run_subst_moves(emat_run* r, emat_subst_result* out) { if (!r) return EMAT_ERR_INVALID_ARGUMENT; return r->d.subst_moves(out); }
 emat_status emat_run_get_hky(emat_run* r, double* mu, double* kappa, double* pi) {

@@ -52,10 +52,9 @@ emat_status emat_site_rate_moves(emat_backend* h, const double* Ttwiddle_l, cons
   out->num_accepted = (int32_t)res[k_sr_num_accepted]; out->num_floored = (int32_t)res[k_sr_num_floored];
   out->delta_log_G = res[k_sr_d_log_G]; out->delta_log_prior_alpha = res[k_sr_d_prior_alpha]; out->delta_log_prior_nu = res[k_sr_d_prior_nu];
   out->sum_nu_old = res[k_sr_sum_nu_old2]; out->sum_nu_new = res[k_sr_sum_nu_new];
-  // the new rates become the model's, by emat_set_evo's rules
+  // the new rates become the model's
   h->nu_l.swap(nu_new);
-  refresh_ref_derived(h);
-  h->model_changed();
+  install_model(h);
   laps.mark("site_rate_moves: 4 copy-back + refresh_ref_derived");
   return EMAT_OK;
 }

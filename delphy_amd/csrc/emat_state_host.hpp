@@ -175,17 +175,16 @@ struct ExpPopScratch {
   DevBuf<emat_exp_pop_step> trace;
 };
 
-// What the substitution-model moves work in (emat_subst_kernels.hpp, emat_subst_host.hpp): the statistics record, the result, the trace; grow-only.
-struct SubstScratch {
-  DevBuf<double> stats, result;
-  DevBuf<emat_subst_step> trace;
-};
+// The substitution statistics both groups below read (emat_subst_stats_host.hpp), from the caller or from the parts on the handle: k_sb_stats_doubles doubles, the last call's.
+struct SubstStatsScratch { DevBuf<double> record; };
 
-// What the APOBEC model's moves work in (emat_mpox_kernels.hpp, emat_mpox_host.hpp) beside the statistics record above: the result, the trace; grow-only.
-struct MpoxScratch {
-  DevBuf<double> result;
-  DevBuf<emat_mpox_round> trace;
+// What a group that runs as one wavefront on that record works in, the substitution-model moves (emat_subst_kernels.hpp, emat_subst_host.hpp) and the APOBEC
+// model's (emat_mpox_kernels.hpp, emat_mpox_host.hpp): the result's doubles and the trace's steps; grow-only.
+template <class Step> struct OneWaveScratch {
+  DevBuf<double> result; DevBuf<Step> trace;
 };
+using SubstScratch = OneWaveScratch<emat_subst_step>;
+using MpoxScratch = OneWaveScratch<emat_mpox_round>;
 
 // What the site-rate moves work in (emat_site_rate_kernels.hpp, emat_site_rate_host.hpp): grow-only, sized by the handle's L at the first call.
 struct SiteRateScratch {
@@ -327,8 +326,9 @@ struct emat_backend {
   SkygridScratch sky;               // what emat_skygrid_moves works in
   ExpPopScratch xp;                 // what emat_exp_pop_moves works in
   SiteRateScratch sr;               // what emat_site_rate_moves works in
+  SubstStatsScratch sbs;            // the statistics the two groups below read (emat_parts_subst_stats, or uploaded by the caller)
   SubstScratch sb;                  // what emat_subst_moves works in
-  MpoxScratch mx;                   // what emat_mpox_moves works in (the statistics record is sb.stats)
+  MpoxScratch mx;                   // what emat_mpox_moves works in
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
   int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs

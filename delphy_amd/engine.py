@@ -105,8 +105,10 @@ _SITE_RATE_TRACE = (_SiteRateResultC, _SiteRateStepC, SITE_RATE_STEP_DTYPE)   # 
 
 
 def _traced_result(cls, res, trace):
-    """A result dataclass of the global moves from its C struct: the struct's scalars under their names, in its order, then the trace."""
-    return cls(*[getattr(res, f.name) for f in fields(cls)[:-1]], trace)
+    """A result dataclass of the global moves from its C struct: the struct's scalars under their names, in its order (a fixed array among them, the
+    substitution result's pi, as a float64 array), then the trace."""
+    values = [getattr(res, f.name) for f in fields(cls)[:-1]]
+    return cls(*[np.array(list(v), np.float64) if isinstance(v, C.Array) else v for v in values], trace)
 
 
 @dataclass
@@ -125,6 +127,13 @@ class SiteRateResult:
 
 
 _KEY_MASK = 0xFFFFFFFFFFFFFFFF   # a move key as the C ABI takes it: the low 64 bits
+
+
+def _traced_call(owner, name: str, args, trace_of, steps: int, trace: bool, result):
+    """The call `name` of the global moves on `owner` (a backend or a run): `args` after its handle, then a C result with room for `steps` trace records; the result's dataclass."""
+    res, tr = _traced_result_c(*trace_of, steps, trace)
+    owner._ck(getattr(owner._lib, name)(owner._h, *args, C.byref(res)), name)
+    return _traced_result(result, res, tr)
 
 
 def _traced_result_c(result_c, step_c, dtype, steps: int, trace: bool):
@@ -321,12 +330,6 @@ class SubstMovesResult:
     pi_left_unit: int
     forced_rejections: int
     trace: Optional[np.ndarray]    # [2 * rounds] records of SUBST_STEP_DTYPE (even: pi steps, odd: kappa steps), or None when not asked for
-
-
-def _subst_result(res: "_SubstResultC", trace) -> "SubstMovesResult":
-    r = _traced_result(SubstMovesResult, res, trace)
-    r.pi = np.array(list(res.pi), np.float64)
-    return r
 
 
 class _MpoxSpecC(C.Structure):
@@ -1351,10 +1354,8 @@ class EmatBackend:
         T = np.ascontiguousarray(Ttwiddle_l, np.float64); M = np.ascontiguousarray(num_muts_l, np.int32)
         if T.shape != (self.num_sites,) or M.shape != (self.num_sites,):
             raise ValueError("Ttwiddle_l and num_muts_l must have one entry per site")
-        res, tr = _traced_result_c(*_SITE_RATE_TRACE, int(num_alpha_steps), trace and num_alpha_steps > 0)
-        self._ck(self._lib.emat_site_rate_moves(self._h, T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int32)), float(alpha), int(num_alpha_steps),
-                                                int(key) & _KEY_MASK, C.byref(res)), "emat_site_rate_moves")
-        return _traced_result(SiteRateResult, res, tr)
+        args = (T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int32)), float(alpha), int(num_alpha_steps), int(key) & _KEY_MASK)
+        return _traced_call(self, "emat_site_rate_moves", args, _SITE_RATE_TRACE, int(num_alpha_steps), trace and num_alpha_steps > 0, SiteRateResult)
 
     def _pop_moves(self, name: str, pop: PopModel, spec, t_ref: float, t_step: float, first_cell: int, k_bar, inner_t, key: int, res):
         """A population group's call emat_<name> on the statistics handed in, or emat_tree_<name> on the resident tree's own where `k_bar` is None."""
@@ -1398,6 +1399,12 @@ class EmatBackend:
         """emat_exp_pop_moves on the statistics of the tree resident in HBM, which never leave it (emat_tree_exp_pop_moves)."""
         return self.exp_pop_moves(pop, spec, t_ref, t_step, 0, None, None, key, trace)
 
+    def _parts_moves(self, name: str, spec, stats, key: int, trace_of, steps: int, trace: bool, result):
+        """A parts' group's call emat_<name> on the statistics handed in (`stats`: the C arguments that carry them), or emat_parts_<name> on those of the parts on
+        this handle where `stats` is None."""
+        sp = spec.c_struct()
+        return _traced_call(self, ("emat_parts_" if stats is None else "emat_") + name, (C.byref(sp), *(stats or ()), int(key) & _KEY_MASK), trace_of, steps, trace, result)
+
     def subst_moves(self, spec: "SubstSpec", Ttwiddle_beta_a, num_muts_beta_ab, root_state_counts, key: int = 0, trace: bool = False) -> "SubstMovesResult":
         """mu_move, then `spec.rounds` times hky_frequencies_move + hky_kappa_move on the device (include/emat_backend.h: emat_subst_moves), from the
         run's summed statistics: Ttwiddle_beta_a [P][4], num_muts_beta_ab [P][4][4] and the state counts at the run's root [4]."""
@@ -1405,31 +1412,29 @@ class EmatBackend:
         T = T.reshape(-1, 4); nP = T.shape[0]
         if M.size != 16 * nP or Cn.size != 4:
             raise ValueError("num_muts_beta_ab must be [P][4][4] for the P of Ttwiddle_beta_a, root_state_counts [4]")
-        sp = spec.c_struct()
-        res, tr = _traced_result_c(*_SUBST_TRACE, 2 * spec.rounds, trace)
-        self._ck(self._lib.emat_subst_moves(self._h, C.byref(sp), nP, T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int64)), Cn.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            int(key) & _KEY_MASK, C.byref(res)), "emat_subst_moves")
-        return _subst_result(res, tr)
+        stats = (nP, T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int64)), Cn.ctypes.data_as(C.POINTER(C.c_int64)))
+        return self._parts_moves("subst_moves", spec, stats, key, _SUBST_TRACE, 2 * spec.rounds, trace, SubstMovesResult)
+
+    def _model_partitions(self) -> int:
+        """P of the model the handle holds: what a caller asks emat_get_evo first, to size what it fetches next."""
+        n = C.c_int32(0)
+        self._ck(self._lib.emat_get_evo(self._h, C.byref(n), None, None, None), "emat_get_evo")
+        return n.value
 
     def parts_subst_stats(self, num_partitions: Optional[int] = None):
         """(Ttwiddle_beta_a [P][4], num_muts_beta_ab [P][4][4], root_state_counts [4]) of the parts on this handle, reduced on the device (emat_parts_subst_stats).
         The call writes for the P of the handle's model, so the arrays are sized by it (emat_get_evo); `num_partitions`, when given, must be that P."""
-        n = C.c_int32(0)
-        self._ck(self._lib.emat_get_evo(self._h, C.byref(n), None, None, None), "emat_get_evo")
-        if num_partitions is not None and int(num_partitions) != n.value:
-            raise ValueError("num_partitions is %d, the handle's model has %d site partitions" % (num_partitions, n.value))
-        num_partitions = n.value
-        T = np.zeros((num_partitions, 4)); M = np.zeros((num_partitions, 4, 4), np.int64); Cn = np.zeros(4, np.int64)
+        nP = self._model_partitions()
+        if num_partitions is not None and int(num_partitions) != nP:
+            raise ValueError("num_partitions is %d, the handle's model has %d site partitions" % (num_partitions, nP))
+        T = np.zeros((nP, 4)); M = np.zeros((nP, 4, 4), np.int64); Cn = np.zeros(4, np.int64)
         self._ck(self._lib.emat_parts_subst_stats(self._h, T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int64)), Cn.ctypes.data_as(C.POINTER(C.c_int64))),
                  "emat_parts_subst_stats")
         return T, M, Cn
 
     def parts_subst_moves(self, spec: "SubstSpec", key: int = 0, trace: bool = False) -> "SubstMovesResult":
         """emat_subst_moves on the statistics of the parts on this handle, which never leave it (emat_parts_subst_moves)."""
-        sp = spec.c_struct()
-        res, tr = _traced_result_c(*_SUBST_TRACE, 2 * spec.rounds, trace)
-        self._ck(self._lib.emat_parts_subst_moves(self._h, C.byref(sp), int(key) & _KEY_MASK, C.byref(res)), "emat_parts_subst_moves")
-        return _subst_result(res, tr)
+        return self._parts_moves("subst_moves", spec, None, key, _SUBST_TRACE, 2 * spec.rounds, trace, SubstMovesResult)
 
     def mpox_moves(self, spec: "MpoxSpec", Ttwiddle_beta_a, num_muts_beta_ab, key: int = 0, trace: bool = False) -> "MpoxMovesResult":
         """`spec.rounds` rounds of the Gibbs draws of mu and rho = mu* / mu of the APOBEC model on the device (include/emat_backend.h: emat_mpox_moves), from the
@@ -1437,24 +1442,16 @@ class EmatBackend:
         T = np.ascontiguousarray(Ttwiddle_beta_a, np.float64); M = np.ascontiguousarray(num_muts_beta_ab, np.int64)
         if T.size != 8 or M.size != 32:
             raise ValueError("Ttwiddle_beta_a must be [2][4] and num_muts_beta_ab [2][4][4]")
-        sp = spec.c_struct()
-        res, tr = _traced_result_c(*_MPOX_TRACE, spec.rounds, trace)
-        self._ck(self._lib.emat_mpox_moves(self._h, C.byref(sp), T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int64)), int(key) & _KEY_MASK, C.byref(res)),
-                 "emat_mpox_moves")
-        return _traced_result(MpoxMovesResult, res, tr)
+        stats = (T.ctypes.data_as(C.POINTER(C.c_double)), M.ctypes.data_as(C.POINTER(C.c_int64)))
+        return self._parts_moves("mpox_moves", spec, stats, key, _MPOX_TRACE, spec.rounds, trace, MpoxMovesResult)
 
     def parts_mpox_moves(self, spec: "MpoxSpec", key: int = 0, trace: bool = False) -> "MpoxMovesResult":
         """emat_mpox_moves on the statistics of the parts on this handle, which never leave it (emat_parts_mpox_moves)."""
-        sp = spec.c_struct()
-        res, tr = _traced_result_c(*_MPOX_TRACE, spec.rounds, trace)
-        self._ck(self._lib.emat_parts_mpox_moves(self._h, C.byref(sp), int(key) & _KEY_MASK, C.byref(res)), "emat_parts_mpox_moves")
-        return _traced_result(MpoxMovesResult, res, tr)
+        return self._parts_moves("mpox_moves", spec, None, key, _MPOX_TRACE, spec.rounds, trace, MpoxMovesResult)
 
     def get_evo(self):
         """(mu [P], pi [P][4], q [P][4][4]) of the model the handle holds (emat_get_evo)."""
-        n = C.c_int32(0); dp = C.POINTER(C.c_double)
-        self._ck(self._lib.emat_get_evo(self._h, C.byref(n), None, None, None), "emat_get_evo")
-        nP = n.value
+        nP = self._model_partitions(); n = C.c_int32(nP); dp = C.POINTER(C.c_double)
         mu = np.zeros(nP); pi = np.zeros((nP, 4)); q = np.zeros((nP, 4, 4))
         self._ck(self._lib.emat_get_evo(self._h, C.byref(n), mu.ctypes.data_as(dp), pi.ctypes.data_as(dp), q.ctypes.data_as(dp)), "emat_get_evo")
         return mu, pi, q
@@ -1616,6 +1613,15 @@ class EmatRun:
             msg = self._lib.emat_run_last_error(self._h)
             raise EmatError("%s: %s (%s)" % (what, STATUS_NAMES.get(st, st), msg.decode() if msg else ""))
 
+    # What sizes the traces of the global moves' calls until a setter says otherwise: the Skygrid's knots and HMC steps, the rounds of the other groups.
+    _sky_knots = 0; _sky_steps = 25; _xp_rounds = 0; _sb_rounds = 0; _mx_rounds = 0
+
+    def _set_moves(self, name: str, on: bool, spec):
+        """A group's setter emat_run_<name>; the C spec comes back, whose rounds (or steps) size the traces of the group's calls."""
+        sp = spec.c_struct()
+        self._ck(getattr(self._lib, name)(self._h, 1 if on else 0, C.byref(sp)), name)
+        return sp
+
     def set_num_parts(self, n: int):
         self._ck(self._lib.emat_run_set_num_parts(self._h, n), "emat_run_set_num_parts")
 
@@ -1706,61 +1712,45 @@ class EmatRun:
 
     def site_rate_moves(self, trace: bool = False) -> "SiteRateResult":
         """One round of site-rate moves while the parts are out (emat_run_site_rate_moves): ten alpha steps and the draw of every nu_l."""
-        res, tr = _traced_result_c(*_SITE_RATE_TRACE, 10, trace)
-        self._ck(self._lib.emat_run_site_rate_moves(self._h, C.byref(res)), "emat_run_site_rate_moves")
-        return _traced_result(SiteRateResult, res, tr)
+        return _traced_call(self, "emat_run_site_rate_moves", (), _SITE_RATE_TRACE, 10, trace, SiteRateResult)
 
     def set_skygrid_moves(self, on: bool = True, spec: "SkygridSpec" = None):
         """The Skygrid population moves once per cycle of do_mcmc_steps, before the repartition (off by default); `spec`: Run's Skygrid settings and the tau to start from."""
-        sp = (spec or SkygridSpec()).c_struct()
-        self._ck(self._lib.emat_run_set_skygrid_moves(self._h, 1 if on else 0, C.byref(sp)), "emat_run_set_skygrid_moves")
-        self._sky_steps = int(sp.hmc_steps)
+        self._sky_steps = int(self._set_moves("emat_run_set_skygrid_moves", on, spec or SkygridSpec()).hmc_steps)
 
     def skygrid_moves(self, trace: bool = False) -> "SkygridMovesResult":
         """One round of the Skygrid moves on the assembled tree (emat_run_skygrid_moves): tau, the zero mode, the HMC on the gammas."""
-        n = getattr(self, "_sky_knots", 0)
-        res, gamma, tr = _skygrid_result_c(n, getattr(self, "_sky_steps", 25), trace)
+        n = self._sky_knots
+        res, gamma, tr = _skygrid_result_c(n, self._sky_steps, trace)
         self._ck(self._lib.emat_run_skygrid_moves(self._h, C.byref(res)), "emat_run_skygrid_moves")
         return SkygridMovesResult(res, gamma[:n], tr)
 
     def set_exp_pop_moves(self, on: bool = True, spec: "ExpPopSpec" = None):
         """The Exponential population moves once per cycle of do_mcmc_steps, before the repartition (off by default); `spec`: Run's settings of the two moves and the rounds."""
-        sp = (spec or ExpPopSpec()).c_struct()
-        self._ck(self._lib.emat_run_set_exp_pop_moves(self._h, 1 if on else 0, C.byref(sp)), "emat_run_set_exp_pop_moves")
-        self._xp_rounds = int(sp.rounds)
+        self._xp_rounds = int(self._set_moves("emat_run_set_exp_pop_moves", on, spec or ExpPopSpec()).rounds)
 
     def exp_pop_moves(self, trace: bool = False) -> "ExpPopMovesResult":
         """One call of the Exponential population moves on the assembled tree (emat_run_exp_pop_moves): `rounds` times the n0 step and the g step."""
-        res, tr = _traced_result_c(*_EXP_POP_TRACE, 2 * getattr(self, "_xp_rounds", 0), trace)
-        self._ck(self._lib.emat_run_exp_pop_moves(self._h, C.byref(res)), "emat_run_exp_pop_moves")
-        return _traced_result(ExpPopMovesResult, res, tr)
+        return _traced_call(self, "emat_run_exp_pop_moves", (), _EXP_POP_TRACE, 2 * self._xp_rounds, trace, ExpPopMovesResult)
 
     def set_subst_moves(self, on: bool = True, spec: "SubstSpec" = None):
         """The substitution-model moves once per cycle of do_mcmc_steps, after the repartition and before the site-rate round (off by default); `spec`: Run's
         mu prior, the three switches and the rounds (its mu, kappa and pi are ignored: the run's own are used)."""
-        sp = (spec or SubstSpec()).c_struct()
-        self._ck(self._lib.emat_run_set_subst_moves(self._h, 1 if on else 0, C.byref(sp)), "emat_run_set_subst_moves")
-        self._sb_rounds = int(sp.rounds)
+        self._sb_rounds = int(self._set_moves("emat_run_set_subst_moves", on, spec or SubstSpec()).rounds)
 
     def subst_moves(self, trace: bool = False) -> "SubstMovesResult":
         """One call of the substitution-model moves while the parts are out (emat_run_subst_moves): the mu draw, then `rounds` times the pi step and the kappa step."""
-        res, tr = _traced_result_c(*_SUBST_TRACE, 2 * getattr(self, "_sb_rounds", 0), trace)
-        self._ck(self._lib.emat_run_subst_moves(self._h, C.byref(res)), "emat_run_subst_moves")
-        return _subst_result(res, tr)
+        return _traced_call(self, "emat_run_subst_moves", (), _SUBST_TRACE, 2 * self._sb_rounds, trace, SubstMovesResult)
 
     def set_mpox(self, on: bool = True, spec: "MpoxSpec" = None):
         """The APOBEC (mpox) model (emat_run_set_mpox): two site partitions cut by the APOBEC context of the sequence at node 0, and its moves once per cycle of
         do_mcmc_steps where the substitution-model moves run; `spec`: mu* to start from, Run's mu prior, its switch and the rounds (its mu is ignored: the run's
         own is used).  Off: one partition and the HKY model again."""
-        sp = (spec or MpoxSpec()).c_struct()
-        self._ck(self._lib.emat_run_set_mpox(self._h, 1 if on else 0, C.byref(sp)), "emat_run_set_mpox")
-        self._mx_rounds = int(sp.rounds)
+        self._mx_rounds = int(self._set_moves("emat_run_set_mpox", on, spec or MpoxSpec()).rounds)
 
     def mpox_moves(self, trace: bool = False) -> "MpoxMovesResult":
         """One call of the APOBEC model's moves while the parts are out (emat_run_mpox_moves): `rounds` times the mu draw and the rho draw."""
-        res, tr = _traced_result_c(*_MPOX_TRACE, getattr(self, "_mx_rounds", 0), trace)
-        self._ck(self._lib.emat_run_mpox_moves(self._h, C.byref(res)), "emat_run_mpox_moves")
-        return _traced_result(MpoxMovesResult, res, tr)
+        return _traced_call(self, "emat_run_mpox_moves", (), _MPOX_TRACE, self._mx_rounds, trace, MpoxMovesResult)
 
     def mpox(self):
         """(mu, mu*) of the APOBEC model as the driver holds them."""
@@ -1788,9 +1778,9 @@ class EmatRun:
 
     def skygrid(self):
         """(gamma, tau) of the Skygrid curve as the driver holds them."""
-        g = np.zeros(max(1, getattr(self, "_sky_knots", 0))); tau = C.c_double()
+        g = np.zeros(max(1, self._sky_knots)); tau = C.c_double()
         self._ck(self._lib.emat_run_get_skygrid(self._h, g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(tau)), "emat_run_get_skygrid")
-        return g[: getattr(self, "_sky_knots", 0)], tau.value
+        return g[: self._sky_knots], tau.value
 
     def site_rates(self):
         """(alpha, nu_l) as the driver holds them."""

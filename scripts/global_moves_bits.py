@@ -1,4 +1,4 @@
-"""The bits the three groups of global moves give (site rates, Skygrid, Exponential population), as SHA-256 digests: to compare two builds of the
+"""The bits the five groups of global moves give (site rates, Skygrid, Exponential population, substitution model, APOBEC model), as SHA-256 digests: to compare two builds of the
 library on one device (the loaded one is the one at EMAT_LIB_PATH, or the tree's own).  Only the public API of delphy_amd/engine.py is used.
 
 A digest is over the bytes of everything a call returns: every scalar, the curve, the trace, the rates; a refusal gives the digest of its text.
@@ -8,6 +8,9 @@ A digest is over the bytes of everything a call returns: every scalar, the curve
                    leapfrog steps.  Exponential: 0, 1 and 50 rounds x g just above and just below 0 (the steps cross it) x min_pop 0 and above.
   synthetic        host statistics with max(num_inner, num_cells) at 1 024 and 1 025, either side of the second workgroup
   site rates       L = 255, 256, 257 and the scenario's own, with 0 and 10 alpha steps, two calls on one handle
+  parts            per tips 33 and 600, 300 sites cut into parts: the substitution-model moves under 1, 2 and 4 site partitions and the APOBEC model's under 2, with 0, 1
+                   and 50 rounds and with each switch off in turn, on the parts' own statistics and on those downloaded from them; the model before every call
+                   is the one the parts went out under.  Each call's result, then emat_get_evo
   run              three cycles of do_mcmc_steps per group on 33 and 600 tips, tree in HBM: the group's parameters after each cycle and tree()
 
     python scripts/global_moves_bits.py > digests.json        # {"emat_build_id": ..., "digests": {case: sha256}}
@@ -113,10 +116,51 @@ def site_rates(out):
                 b.close()
 
 
+def parts_groups(out):
+    for tips in (33, 600):
+        sc = make_scenario("C1", num_tips=tips, num_sites=300)
+        cutter = d.EmatRun(None, sc.tree, sc.ref, 9)                                 # the product's host driver cuts the tree (no device needed)
+        try:
+            cutter.set_num_parts(4 if tips > 100 else 3); cutter.repartition()
+            n, root_part = cutter.num_parts()
+            parts, incl, seeds = zip(*[cutter.part(i) for i in range(n)])
+            ref = cutter.tree()[1]
+        finally:
+            cutter.close()
+        L = sc.num_sites
+        models = [("subst", P, ([sc.mu] * P, [sc.pi] * P, [d.hky_q_matrix(sc.kappa + p, sc.pi) for p in range(P)], np.ones(L), np.arange(L) % P)) for P in (1, 2, 4)]
+        models.append(("mpox", 2, ([sc.mu] * 2, [[0.25] * 4] * 2, list(d.engine.mpox_q_matrices(0.5)), np.ones(L), np.arange(L) % 2)))
+        for group, P, evo in models:
+            b = d.EmatBackend(L)
+            try:
+                b.set_ref_sequence(ref); b.set_evo(*evo); b.set_flags(sc.t_max_tip, False, True)
+                b.upload_parts(list(parts), list(incl), list(seeds)); b.build_coalescent_parts(sc.pop, root_part, sc.default_t_step())
+                where = "parts %s, tips %d, %d site partitions: " % (group, tips, P)
+                out[where + "parts_subst_stats"] = digest(lambda: b.parts_subst_stats(P))
+                T, M, Cn = b.parts_subst_stats(P)
+                if group == "subst":
+                    base = d.SubstSpec(mu=sc.mu, kappa=sc.kappa, pi=tuple(sc.pi))
+                    specs = [("%d rounds" % r, dataclasses.replace(base, rounds=r)) for r in (0, 1, 50)] + [(sw + " off", dataclasses.replace(base, **{sw: False})) for sw in ("do_mu", "do_pi", "do_kappa")]
+                    calls = {"host": lambda sp, key: b.subst_moves(sp, T, M, Cn, key=key, trace=True), "parts": lambda sp, key: b.parts_subst_moves(sp, key=key, trace=True)}
+                else:
+                    base = d.MpoxSpec(mu=sc.mu, mu_star=0.5 * sc.mu)
+                    specs = [("%d rounds" % r, dataclasses.replace(base, rounds=r)) for r in (0, 1, 50)] + [("do_mu off", dataclasses.replace(base, do_mu=False))]
+                    calls = {"host": lambda sp, key: b.mpox_moves(sp, T, M, key=key, trace=True), "parts": lambda sp, key: b.parts_mpox_moves(sp, key=key, trace=True)}
+                for key, (name, sp) in enumerate(specs):
+                    for source, call in calls.items():
+                        b.set_evo(*evo)
+                        out[where + name + ", " + source] = digest(lambda: call(sp, 40 + key))
+                        out[where + name + ", " + source + ": get_evo"] = digest(lambda: b.get_evo())
+            finally:
+                b.close()
+
+
 def run_cycles(out):
     groups = {"site rates": ("C1", lambda r: r.set_site_rate_moves(True, 1.0), lambda r: (np.float64(r.site_rates()[0]), r.site_rates()[1])),
               "Skygrid": ("C3", lambda r: r.set_skygrid_moves(True, d.SkygridSpec(tau=2.0, low_gamma_barrier_enabled=True)), lambda r: (r.skygrid()[0], np.float64(r.skygrid()[1]))),
-              "Exponential": ("C2", lambda r: r.set_exp_pop_moves(True, d.ExpPopSpec(inv_n0_prior_alpha=1.0, inv_n0_prior_beta=50.0)), lambda r: (np.asarray(r.exp_pop()),))}
+              "Exponential": ("C2", lambda r: r.set_exp_pop_moves(True, d.ExpPopSpec(inv_n0_prior_alpha=1.0, inv_n0_prior_beta=50.0)), lambda r: (np.asarray(r.exp_pop()),)),
+              "substitution model": ("C1", lambda r: r.set_subst_moves(True, d.SubstSpec()), lambda r: (np.float64(r.hky()[:2]), r.hky()[2])),
+              "APOBEC model": ("C1", lambda r: r.set_mpox(True, d.MpoxSpec()), lambda r: (np.float64(r.mpox()),))}
     for tips in (33, 600):
         for group, (kind, switch_on, params) in groups.items():
             sc = make_scenario(kind, num_tips=tips, num_sites=300, **(dict(skygrid_log_linear=True) if kind == "C3" else {}))
@@ -136,7 +180,7 @@ def run_cycles(out):
 
 def main():
     out = {}
-    population_groups(out); site_rates(out); run_cycles(out)
+    population_groups(out); site_rates(out); parts_groups(out); run_cycles(out)
     print(json.dumps({"emat_build_id": d.library_build_id(), "digests": out}, indent=1))
 
 
