@@ -714,15 +714,18 @@ EMAT_D double delta_lambda_across_node_missations_fresh(Ctx& c, int node) {
 // The same number, remembered per node (k_miss_dl_unknown, emat_slab.hpp): two cumQ gathers per interval and a reference-sequence
 // load per from-state, all dependent and all on the chain's critical path, for a value that only a topology move can change.  What is
 // stored is what the function above returned for the node's lists as they are, so a hit and a miss hand out the same bits.
+// The miss is out of line: the test and the hit are all that a caller carries (an inner-node displacement asks for both children, and
+// carried the two gather loops twice).
+EMAT_DN double delta_lambda_across_node_missations_miss(Ctx& c, int node) { EMAT_TIMED(0);   /* miss_dl: not known, computed (1 - calls of this scope / calls of the one below = the hit rate) */
+  const double r = delta_lambda_across_node_missations_fresh(c, node);
+  miss_dl_of(c)[node] = (uint64_t)__double_as_longlong(r);
+  return r;
+}
 EMAT_D double delta_lambda_across_node_missations(Ctx& c, int node) { EMAT_TIMED(0);   /* miss_dl: every request */
   uint64_t* e = miss_dl_of(c) + node;
   const uint64_t bits = *e;
   if (bits != k_miss_dl_unknown) return __longlong_as_double((long long)bits);
-  double r;
-  { EMAT_TIMED(0);   /* miss_dl: not known, computed (1 - calls of this scope / calls of the one above = the hit rate) */
-    r = delta_lambda_across_node_missations_fresh(c, node); }
-  *e = (uint64_t)__double_as_longlong(r);
-  return r;
+  return delta_lambda_across_node_missations_miss(c, node);
 }
 // kMemo = false: every lane of a whole-part recomputation asks for its own nodes, and leaves the remembered values alone
 template <bool kMemo = true> EMAT_D double delta_lambda_across_branch(Ctx& c, int node) {   // h:140-155
@@ -881,15 +884,20 @@ EMAT_DF SkyKnots skygrid_knots_uniform(const EMAT_CONST_AS double* x, const EMAT
 EMAT_DF void skygrid_knots_arrive(SkyKnots& a, SkyKnots& b) {
   asm volatile("" : "+s"(a.xa), "+s"(a.xb), "+s"(a.ga), "+s"(a.gb), "+s"(b.xa), "+s"(b.xb), "+s"(b.ga), "+s"(b.gb));
 }
-EMAT_DF double skygrid_log_N_uniform(const EMAT_CONST_AS double* x, const EMAT_CONST_AS double* ga, int n, int type, double t, const SkyKnots& s) {   // skygrid_interval + skygrid_log_N
-  int k = s.k; const int M = n - 1;
-  if ((k == 0 || s.xa < t) && (k == n || !(s.xb < t))) {   // the first test of each loop below: k is lower_bound
-    if (k == 0) return s.ga;        // ga[0]
-    if (k > M) return s.gb;         // ga[M]
-    if (type == 1) return s.gb;     // ga[k]
-    const double cc = (t - s.xa) / (s.xb - s.xa);
-    return (1 - cc) * s.ga + cc * s.gb;
-  }
+// Does the guess stand?  The first test of each of skygrid_log_N_search's loops: k is lower_bound.
+EMAT_DF bool skygrid_guess_stands(int n, double t, const SkyKnots& s) { return (s.k == 0 || s.xa < t) && (s.k == n || !(s.xb < t)); }
+// The value at a time whose guess stands, from what the batch loaded: the search's last four lines on the same operands.
+EMAT_DF double skygrid_log_N_batched(int n, int type, double t, const SkyKnots& s) {
+  const int k = s.k, M = n - 1;
+  if (k == 0) return s.ga;        // ga[0]
+  if (k > M) return s.gb;         // ga[M]
+  if (type == 1) return s.gb;     // ga[k]
+  const double cc = (t - s.xa) / (s.xb - s.xa);
+  return (1 - cc) * s.ga + cc * s.gb;
+}
+// skygrid_interval + skygrid_log_N from a guess k, any guess: the loops end at lower_bound wherever they start.
+EMAT_DF double skygrid_log_N_search(const EMAT_CONST_AS double* x, const EMAT_CONST_AS double* ga, int n, int type, double t, int k) {
+  const int M = n - 1;
   while (k > 0 && !(x[k - 1] < t)) --k;
   while (k < n && x[k] < t) ++k;
   if (k == 0) return ga[0];
@@ -897,6 +905,12 @@ EMAT_DF double skygrid_log_N_uniform(const EMAT_CONST_AS double* x, const EMAT_C
   if (type == 1) return ga[k];
   const double cc = (t - x[k - 1]) / (x[k] - x[k - 1]);
   return (1 - cc) * ga[k - 1] + cc * ga[k];
+}
+// The ratio where one of the two guesses does not stand (never on an even grid, but for a time on a knot): both times through the
+// search, out of line, so that the displacements carry the batch alone.  A time whose guess stood gets from the search what the batch
+// gives it -- the loops end at once, and x[k - 1], x[k], ga[k - 1], ga[k] are what the batch loaded.
+EMAT_DN double skygrid_log_ratio_search(const EMAT_CONST_AS double* x, const EMAT_CONST_AS double* ga, int n, int type, double t_new, double t_old, int k_new, int k_old) {
+  return skygrid_log_N_search(x, ga, n, type, t_new, k_new) - skygrid_log_N_search(x, ga, n, type, t_old, k_old);
 }
 EMAT_DF double log_pop_ratio_uniform(const PopTable* pp, double t_new, double t_old) {
   const EMAT_CONST_AS PopTable* p = uniform_const_ptr(pp);
@@ -912,7 +926,8 @@ EMAT_DF double log_pop_ratio_uniform(const PopTable* pp, double t_new, double t_
     SkyKnots at_new = skygrid_knots_uniform(x, ga, n, skygrid_guess_uniform(t_new, x0, inv_dx, n));
     SkyKnots at_old = skygrid_knots_uniform(x, ga, n, skygrid_guess_uniform(t_old, x0, inv_dx, n));
     skygrid_knots_arrive(at_new, at_old);
-    return skygrid_log_N_uniform(x, ga, n, type, t_new, at_new) - skygrid_log_N_uniform(x, ga, n, type, t_old, at_old);
+    if (skygrid_guess_stands(n, t_new, at_new) && skygrid_guess_stands(n, t_old, at_old)) return skygrid_log_N_batched(n, type, t_new, at_new) - skygrid_log_N_batched(n, type, t_old, at_old);
+    return skygrid_log_ratio_search(x, ga, n, type, t_new, t_old, at_new.k, at_old.k);
   }
   const double t0 = p->p[0], n0 = p->p[1], gr = p->p[2], floor_n = p->p[3];
   double a = n0 * m_exp((t_new - t0) * gr); a = floor_n > a ? floor_n : a;
@@ -1156,12 +1171,18 @@ EMAT_DF double coal_cell_term(const Ctx& c, const Cells& k, int w, double new_k,
       +0.5 * (new_k * new_k - old_k * old_k) * na
       - (k.ktw_p[w] * na - ktw + 0.5) * (new_k - old_k));
 }
-// cpp:388-459
-template <bool kGrow = true> EMAT_DF double coal_delta_on_add_interval(Ctx& c, double min_t, double max_t, double delta_k, ByteCount& n) { EMAT_TIMED(0);
-  { int cm = cell_for(c, max_t); if (cm < hdr_of(c)->cell_first || cm >= hdr_of(c)->n_cells_total) { EMAT_FAIL(c, k_part_internal); return 0.0; } }
+// cpp:388-459, in two steps.  The first is what comes before the walk: both ends must lie in the part's window, which only the root
+// part may stretch towards the past (coal_grow, the one call in here).  False: the delta is 0.0, the part has failed.
+template <bool kGrow = true> EMAT_DF bool coal_delta_admit_interval(Ctx& c, double min_t, double max_t) {
+  { int cm = cell_for(c, max_t); if (cm < hdr_of(c)->cell_first || cm >= hdr_of(c)->n_cells_total) { EMAT_FAIL(c, k_part_internal); return false; } }
   coal_ensure_space<kGrow>(c, min_t);
-  if (c.failed) return 0.0;
+  return !c.failed;
+}
+// The walk over the cells of an admitted interval.  `up`: the interval gains a lineage (delta_k = +1.0) or loses one (-1.0); the products
+// delta_k * x are exact and the sums old_k + delta_k have the operands they had when delta_k was a constant.
+EMAT_DF double coal_delta_walk_interval(Ctx& c, double min_t, double max_t, bool up, ByteCount& n) { EMAT_TIMED(0);
   if (min_t == max_t) return 0.0;
+  const double delta_k = up ? +1.0 : -1.0;
   Cells k = cells_of(c);
   const int first = hdr_of(c)->cell_first; const double ts = hdr_of(c)->t_step;
   int cell_start = cell_for(c, max_t), cell_end = cell_for(c, min_t);
@@ -1184,13 +1205,28 @@ template <bool kGrow = true> EMAT_DF double coal_delta_on_add_interval(Ctx& c, d
   EMAT_COUNT(c, 13, cell_end - cell_start + 1); EMAT_COUNT(c, 14, 1);
   return d;
 }
-template <bool kGrow = true> EMAT_DF double coal_delta_displace_coalescence(Ctx& c, double old_t, double new_t, ByteCount& n) { EMAT_TIMED(0);   // cpp:310-326
-  double d = (old_t <= new_t) ? coal_delta_on_add_interval<kGrow>(c, old_t, new_t, -1.0, n) : coal_delta_on_add_interval<kGrow>(c, new_t, old_t, +1.0, n);
+// The reference calls its delta once per direction of a displacement, min_t and max_t in place; inlined, that was the whole walk twice in
+// every caller.  Here the ordered pair is selected and the walk exists once.  `fwd` is the reference's comparison (a NaN time takes the
+// second arm).  `up_if_fwd`: a tip moving towards the present adds a lineage to the interval, a coalescence takes one away.
+// Where the admission can call (kGrow), the pair is selected again after it, from the two times a caller holds across the call anyway:
+// the empty asm keeps the compiler from carrying the first selection, and the flag, over the call beside them (stack of the root part's moves).
+template <bool kGrow, bool kOneWalk> EMAT_DF double coal_delta_displace(Ctx& c, double old_t, double new_t, bool up_if_fwd, ByteCount& n) {
+  bool fwd = old_t <= new_t;
+  if (!kOneWalk) {   // the reference's spelling
+    if (fwd) return coal_delta_admit_interval<kGrow>(c, old_t, new_t) ? coal_delta_walk_interval(c, old_t, new_t, up_if_fwd, n) : 0.0;
+    return coal_delta_admit_interval<kGrow>(c, new_t, old_t) ? coal_delta_walk_interval(c, new_t, old_t, !up_if_fwd, n) : 0.0;
+  }
+  if (!coal_delta_admit_interval<kGrow>(c, fwd ? old_t : new_t, fwd ? new_t : old_t)) return 0.0;
+  if (kGrow) { asm volatile("" : "+v"(old_t), "+v"(new_t)); fwd = old_t <= new_t; }
+  return coal_delta_walk_interval(c, fwd ? old_t : new_t, fwd ? new_t : old_t, fwd == up_if_fwd, n);
+}
+template <bool kGrow = true, bool kOneWalk = true> EMAT_DF double coal_delta_displace_coalescence(Ctx& c, double old_t, double new_t, ByteCount& n) { EMAT_TIMED(0);   // cpp:310-326
+  double d = coal_delta_displace<kGrow, kOneWalk>(c, old_t, new_t, false, n);
   { EMAT_TIMED(0); d -= log_pop_ratio_uniform(c.pop, new_t, old_t); }
   return d;
 }
-template <bool kGrow = true> EMAT_DF double coal_delta_displace_tip(Ctx& c, double old_t, double new_t, ByteCount& n) {           // cpp:337-353
-  return (old_t <= new_t) ? coal_delta_on_add_interval<kGrow>(c, old_t, new_t, +1.0, n) : coal_delta_on_add_interval<kGrow>(c, new_t, old_t, -1.0, n);
+template <bool kGrow = true, bool kOneWalk = true> EMAT_DF double coal_delta_displace_tip(Ctx& c, double old_t, double new_t, ByteCount& n) {           // cpp:337-353
+  return coal_delta_displace<kGrow, kOneWalk>(c, old_t, new_t, true, n);
 }
 template <bool kGrow = true> EMAT_DF void coal_coalescence_displaced(Ctx& c, double old_t, double new_t, ByteCount& n) {           // cpp:301-308
   coal_ensure_space<kGrow>(c, new_t);

@@ -92,7 +92,10 @@ EMAT_NOTAIL EMAT_DN void spr_move_core(Ctx& c, int X, int new_branch, double new
 // The three simple moves are compiled twice: kRoot = true for the part that holds the run's root (its root node may be
 // displaced, its coalescent grid may grow, branch reforms next to the root go through spr_move_core) and kRoot = false for
 // every other part, where none of that can happen: those versions contain no root-only code, and their only calls are the
-// out-of-line transcendentals (m_log, m_exp, ...).
+// out-of-line transcendentals (m_log, m_exp, ...) and the cold halves of the Skygrid ratio and of a node's remembered rate change.
+// The kRoot = false versions walk the coalescent cells of a displacement once (coal_delta_displace, kOneWalk); the root part's keep the
+// reference's walk per direction: with one walk the HBM variant's run_chain<true> spills one register more across its calls, its frame
+// goes from 32 to 48 bytes, and the kernels' ScratchSize from 320 to 336 -- for one part of a run.
 // Each is a body that counts its algorithmic bytes into `n`, whichever way it leaves, and a frame that adds them to the context once.
 template <bool kRoot> EMAT_DF void inner_node_displace_body(Ctx& c, ByteCount& n) {   // subrun.cpp:148-232
   begin_move(c, k_inner_node_displace);
@@ -147,7 +150,7 @@ template <bool kRoot> EMAT_DF void inner_node_displace_body(Ctx& c, ByteCount& n
   if (new_t == t_min || new_t == t_max) return;
   if (kRoot) { if (coal_needs_cells(c, new_t)) { stop_for_cells(c, k_inner_node_displace); return; } }   // nothing has changed yet
   double delta_log_G = d_logG_dt * (new_t - old_t);
-  double delta_log_prior = coal_delta_displace_coalescence<kRoot>(c, old_t, new_t, n);
+  double delta_log_prior = coal_delta_displace_coalescence<kRoot, !kRoot>(c, old_t, new_t, n);
   if (c.failed) return;
   double log_mh = delta_log_G + delta_log_prior - log_alpha_ratio;
   bool acc;
@@ -184,7 +187,7 @@ template <bool kRoot> EMAT_DF void tip_displace_body(Ctx& c, ByteCount& n, int n
   double log_alpha_ratio = d_logG_dt * (new_t - old_t);
   if (new_t == t_min || new_t == t_max) return;
   double delta_log_G = d_logG_dt * (new_t - old_t);
-  double delta_log_prior = coal_delta_displace_tip<kRoot>(c, old_t, new_t, n);
+  double delta_log_prior = coal_delta_displace_tip<kRoot, !kRoot>(c, old_t, new_t, n);
   if (c.failed) return;
   double log_mh = delta_log_G + delta_log_prior - log_alpha_ratio;
   bool acc = mh_accept(c, log_mh);
