@@ -6,6 +6,7 @@ bench.py, __graft_entry__.py and the tests.  There is no CPU fallback: construct
 without the built library or without a HIP device raises.
 """
 from .engine import (  # noqa: F401
+    Alignment,
     EmatBackend,
     EmatError,
     EmatMultiRun,
@@ -30,5 +31,6 @@ from .engine import (  # noqa: F401
     library_path,
     load_library,
     make_synthetic_emat,
+    seq_id_date_range,
     source_build_id,
 )

@@ -39,6 +39,7 @@
 #include "emat_exp_pop_kernels.hpp"     // the Exponential population moves: n0 and the growth rate
 #include "emat_subst_kernels.hpp"       // the substitution-model moves: mu, the HKY frequencies and kappa
 #include "emat_mpox_kernels.hpp"        // the APOBEC (mpox) model's moves: Gibbs rounds of mu and rho = mu* / mu
+#include "emat_align_kernels.hpp"       // aligned sequences in: packed rows, site counts, the consensus, every tip's deltas and missing runs
 #include "emat_state_host.hpp"      // buffers, host records, emat_backend and the transitions of its part state
 #include "emat_slab_host.hpp"       // slab codec, geometry, size classes
 #include "emat_pass_host.hpp"       // materialize, launch_moves, finish_pass, the two pulls
@@ -661,3 +662,4 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 #include "emat_subst_stats_host.hpp"    // the parts' substitution statistics and the frame of the two groups that read them
 #include "emat_subst_host.hpp"
 #include "emat_mpox_host.hpp"
+#include "emat_align_host.hpp"          // the alignment store's entry points

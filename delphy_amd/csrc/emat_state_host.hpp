@@ -229,6 +229,27 @@ struct MccHost {
   void release() { drop(parent); drop(c0); drop(c1); drop(root); drop(t); drop(fp); drop(keys); drop(ntips); drop(arrive); drop(corr); drop(counts); drop(hist); drop(exact); release_mutations(); capacity = 0; count = 0; derived_M = 0; table_log2_hint = 0; }
 };
 
+// The alignment store and what emat_align_finish works in (emat_align_kernels.hpp, emat_align_host.hpp).  The store is sized by emat_align_begin, exactly;
+// everything else is grow-only.  `attached` is the FASTA loader's record of the rows (names, dates: emat_fasta.cpp), which lives and dies with the store.
+struct AlignHost {
+  bool bound = false, finished = false;
+  int64_t max_rows = 0, rows = 0, row_bytes = 0;
+  DevBuf<uint8_t> packed, chars, ref, delta_to; DevBuf<unsigned long long> bad; DevBuf<long long> totals;
+  DevBuf<int32_t> counts, tip_row, n_delta, n_iv, n_not_n, delta_off, miss_off, delta_site, miss_start, miss_end;
+  PinnedBytes row_buf[2]; hipEvent_t row_ev[2] = {nullptr, nullptr}, copy_ev = nullptr; bool row_ev_pending[2] = {false, false};   // emat_align_row_buffer
+  std::vector<int32_t> row_status, row_bad_site, row_not_n; std::vector<uint8_t> row_bad_byte;                                      // the last finish's, per input row
+  emat_align_report report{};
+  void* attached = nullptr; void (*attached_free)(void*) = nullptr;
+  void drop_attached() { if (attached && attached_free) attached_free(attached); attached = nullptr; attached_free = nullptr; }
+  template <class T> static void drop(DevBuf<T>& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 0; b.n_grown = false; }
+  void release() {
+    drop(packed); drop(chars); drop(ref); drop(delta_to); drop(bad); drop(totals); drop(counts); drop(tip_row); drop(n_delta); drop(n_iv); drop(n_not_n);
+    drop(delta_off); drop(miss_off); drop(delta_site); drop(miss_start); drop(miss_end);
+    bound = false; finished = false; max_rows = 0; rows = 0;
+  }
+  ~AlignHost() { drop_attached(); for (hipEvent_t e : {row_ev[0], row_ev[1], copy_ev}) if (e) (void)hipEventDestroy(e); }
+};
+
 }  // namespace emat
 
 using namespace emat;
@@ -330,6 +351,7 @@ struct emat_backend {
   SubstScratch sb;                  // what emat_subst_moves works in
   MpoxScratch mx;                   // what emat_mpox_moves works in
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
+  AlignHost al;                     // the aligned rows kept in HBM (emat_align_*) and the tip descriptors made from them
   int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs
   BuiltTree built;                  // what emat_tree_build_usher_like made, until it is fetched (emat_tree_built_get)

@@ -447,6 +447,33 @@ class TipDescs:
                           _ptr(self.delta_to, C.c_uint8), _ptr(self.miss_offset, C.c_int32), _ptr(self.miss_start, C.c_int32), _ptr(self.miss_end, C.c_int32))
 
 
+class _AlignReportC(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("num_tips", C.c_int32), ("num_invalid", C.c_int32), ("num_undated", C.c_int32),
+                ("num_deltas", C.c_int64), ("num_intervals", C.c_int64), ("num_precision_loss", C.c_int64)]
+
+
+class _AlignArraysC(C.Structure):
+    _fields_ = [("delta_offset", C.POINTER(C.c_int32)), ("delta_site", C.POINTER(C.c_int32)), ("delta_to", C.POINTER(C.c_uint8)),
+                ("miss_offset", C.POINTER(C.c_int32)), ("miss_start", C.POINTER(C.c_int32)), ("miss_end", C.POINTER(C.c_int32)),
+                ("ref_sequence", C.POINTER(C.c_uint8)), ("counts", C.POINTER(C.c_int32)), ("row_status", C.POINTER(C.c_int32)),
+                ("row_bad_site", C.POINTER(C.c_int32)), ("row_bad_byte", C.POINTER(C.c_uint8)), ("row_precision_loss", C.POINTER(C.c_int32))]
+
+
+class _FastaReportC(C.Structure):
+    _fields_ = [("num_records", C.c_int32), ("num_dated", C.c_int32), ("names_bytes", C.c_int64), ("rows", _AlignReportC)]
+
+
+class Alignment:
+    """What emat_align_finish made of the rows pushed (include/emat_backend.h: emat_align_report, emat_align_arrays): `tips`, a TipDescs
+    without dates unless they were given; `ref`, the given reference sequence or the consensus; `counts` [L, 4]; per input row `row_status`
+    (tip index, -1 undated, -2 invalid), `row_bad_site`, `row_bad_byte` and `row_precision_loss`; and the totals in `report`."""
+
+    def __init__(self, tips, ref, counts, row_status, row_bad_site, row_bad_byte, row_precision_loss, report):
+        self.tips = tips; self.ref = ref; self.counts = counts
+        self.row_status = row_status; self.row_bad_site = row_bad_site; self.row_bad_byte = row_bad_byte; self.row_precision_loss = row_precision_loss
+        self.report = report
+
+
 class _ConfigC(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_sites", C.c_int32), ("max_parts", C.c_int32), ("slab_slack", C.c_double),
                 ("trace_moves", C.c_int32), ("use_lds", C.c_int32)]
@@ -689,6 +716,12 @@ def load_library():
         "emat_run_set_exp_pop_moves": [R, i32, P(_ExpPopSpecC)], "emat_run_exp_pop_moves": [R, P(_ExpPopResultC)], "emat_run_get_exp_pop": [R, P(dbl), P(dbl)],
         "emat_run_set_skygrid_moves": [R, i32, P(_SkygridSpecC)], "emat_run_skygrid_moves": [R, P(_SkygridResultC)], "emat_run_get_skygrid": [R, P(dbl), P(dbl)],
         "emat_run_set_site_rate_moves": [R, i32, dbl], "emat_run_site_rate_moves": [R, P(_SiteRateResultC)], "emat_run_get_site_rates": [R, P(dbl), P(dbl)],
+        "emat_align_begin": [B, i64], "emat_align_row_buffer": [B, i32, i64, P(P(C.c_uint8))], "emat_align_push_rows": [B, i32, P(C.c_uint8), i64],
+        "emat_align_finish": [B, P(C.c_uint8), P(C.c_uint8), P(_AlignReportC)], "emat_align_sizes": [B, P(_AlignReportC)], "emat_align_get": [B, P(_AlignArraysC)],
+        "emat_align_attach": [B, C.c_void_p, C.c_void_p], "emat_align_refuse": [B, C.c_int, C.c_char_p],
+        "emat_seq_id_date_range": [C.c_char_p, P(dbl), P(dbl), P(i32)], "emat_fasta_frame_memory": [B, P(C.c_uint8), i64, P(_FastaReportC)],
+        "emat_fasta_load_memory": [B, P(C.c_uint8), i64, P(C.c_uint8), i32, P(_FastaReportC)], "emat_fasta_load": [B, C.c_char_p, P(C.c_uint8), i32, P(_FastaReportC)],
+        "emat_fasta_sizes": [B, P(_FastaReportC)], "emat_fasta_get": [B, C.c_char_p, P(i64), P(C.c_float), P(C.c_float), P(C.c_uint8)],
     }
     M = C.c_void_p
     sigs.update({
@@ -716,10 +749,21 @@ def load_library():
     lib.emat_multi_num_shards.argtypes = [M]; lib.emat_multi_num_shards.restype = C.c_int32
     lib.emat_multi_backend.argtypes = [M, i32]; lib.emat_multi_backend.restype = C.c_void_p
     lib.emat_multi_shard.argtypes = [M, i32]; lib.emat_multi_shard.restype = C.c_void_p
+    lib.emat_align_attached.argtypes = [B]; lib.emat_align_attached.restype = C.c_void_p
+    lib.emat_align_num_sites.argtypes = [B]; lib.emat_align_num_sites.restype = C.c_int32
     lib.emat_synth_destroy.argtypes = [S]
     lib.emat_synth_destroy.restype = None
     _lib = lib
     return lib
+
+
+def seq_id_date_range(seq_id: str):
+    """(t_min, t_max) in days since 2020-01-01 from the date at the end of a sequence id, or None (include/emat_host.h: emat_seq_id_date_range)."""
+    lo, hi, ok = C.c_double(), C.c_double(), C.c_int32()
+    st = load_library().emat_seq_id_date_range(seq_id.encode(), C.byref(lo), C.byref(hi), C.byref(ok))
+    if st != 0:
+        raise EmatError("emat_seq_id_date_range: %s" % STATUS_NAMES.get(st, st))
+    return (lo.value, hi.value) if ok.value else None
 
 
 def hky_q_matrix(kappa: float, pi: Sequence[float]) -> np.ndarray:
@@ -1554,6 +1598,80 @@ class EmatBackend:
         ref = np.zeros(self.num_sites, np.uint8)
         self._ck(self._lib.emat_tree_built_ref(self._h, ref.ctypes.data_as(C.POINTER(C.c_uint8))), "emat_tree_built_ref")
         return t.trimmed(), ref, dict(guide_deltas=rep[0], refined_deltas=rep[1], spr_deltas=rep[2], rooting="regression" if rep[3] == 0 else "midpoint")
+
+    def align_begin(self, max_rows: int) -> None:
+        """Binds the alignment store to `max_rows` rows of num_sites characters (include/emat_backend.h: emat_align_begin); 0 releases it."""
+        self._ck(self._lib.emat_align_begin(self._h, max_rows), "emat_align_begin")
+
+    def align_push(self, rows, row_stride: Optional[int] = None) -> None:
+        """Pushes rows of ASCII characters: a (rows, >= num_sites) uint8 array whose row length is the stride, or bytes with `row_stride`."""
+        a = np.frombuffer(rows, np.uint8) if isinstance(rows, (bytes, bytearray)) else np.ascontiguousarray(rows, np.uint8)
+        if a.ndim == 2:
+            n, stride = a.shape
+        else:
+            stride = self.num_sites if row_stride is None else row_stride
+            n = 0 if a.size == 0 else (a.size - self.num_sites) // stride + 1
+        self._ck(self._lib.emat_align_push_rows(self._h, n, _ptr(a, C.c_uint8), stride), "emat_align_push_rows")
+
+    def align_finish(self, ref=None, row_dated=None) -> "Alignment":
+        """The reference sequence (`ref`, or the consensus) and, of the rows that are valid and dated, the tip descriptors (emat_align_finish, emat_align_get)."""
+        ref_c = None if ref is None else np.ascontiguousarray(ref, np.uint8)
+        dated_c = None if row_dated is None else np.ascontiguousarray(row_dated, np.uint8)
+        rep = _AlignReportC()
+        self._ck(self._lib.emat_align_finish(self._h, None if ref_c is None else _ptr(ref_c, C.c_uint8), None if dated_c is None else _ptr(dated_c, C.c_uint8), C.byref(rep)), "emat_align_finish")
+        return self._align_get(rep)
+
+    def _align_get(self, rep: "_AlignReportC") -> "Alignment":
+        T, R, L = rep.num_tips, int(rep.num_rows), self.num_sites
+        d_off = np.zeros(T + 1, np.int32); d_site = np.zeros(rep.num_deltas, np.int32); d_to = np.zeros(rep.num_deltas, np.uint8)
+        m_off = np.zeros(T + 1, np.int32); m_start = np.zeros(rep.num_intervals, np.int32); m_end = np.zeros(rep.num_intervals, np.int32)
+        ref = np.zeros(L, np.uint8); counts = np.zeros((L, 4), np.int32)
+        status = np.zeros(R, np.int32); bad_site = np.zeros(R, np.int32); bad_byte = np.zeros(R, np.uint8); loss = np.zeros(R, np.int32)
+        arrays = _AlignArraysC(_ptr(d_off, C.c_int32), _ptr(d_site, C.c_int32), _ptr(d_to, C.c_uint8), _ptr(m_off, C.c_int32), _ptr(m_start, C.c_int32), _ptr(m_end, C.c_int32),
+                               _ptr(ref, C.c_uint8), _ptr(counts, C.c_int32), _ptr(status, C.c_int32), _ptr(bad_site, C.c_int32), _ptr(bad_byte, C.c_uint8), _ptr(loss, C.c_int32))
+        self._ck(self._lib.emat_align_get(self._h, C.byref(arrays)), "emat_align_get")
+        nan = np.full(T, np.nan, np.float32)
+        tips = TipDescs(nan, nan.copy(), d_off, d_site, d_to, m_off, m_start, m_end)
+        report = {k: int(getattr(rep, k)) for k, _ in _AlignReportC._fields_}
+        return Alignment(tips, ref, counts, status, bad_site, bad_byte, loss, report)
+
+    def fasta_records(self):
+        """What the last load or framing left on the handle: (names, lengths, t_min, t_max, dated), one entry per record (emat_fasta_get)."""
+        rep = _FastaReportC()
+        self._ck(self._lib.emat_fasta_sizes(self._h, C.byref(rep)), "emat_fasta_sizes")
+        n = rep.num_records
+        names = C.create_string_buffer(max(int(rep.names_bytes), 1))
+        lengths = np.zeros(n, np.int64); t_min = np.zeros(n, np.float32); t_max = np.zeros(n, np.float32); dated = np.zeros(n, np.uint8)
+        self._ck(self._lib.emat_fasta_get(self._h, names, _ptr(lengths, C.c_int64), _ptr(t_min, C.c_float), _ptr(t_max, C.c_float), _ptr(dated, C.c_uint8)), "emat_fasta_get")
+        return [x.decode("utf-8", "replace") for x in names.raw[: int(rep.names_bytes)].split(b"\0")[:n]], lengths, t_min, t_max, dated
+
+    def fasta_frame(self, text: bytes):
+        """Frames the records of a FASTA text without a device (emat_fasta_frame_memory); returns what fasta_records returns."""
+        a = np.frombuffer(text, np.uint8)
+        self._ck(self._lib.emat_fasta_frame_memory(self._h, _ptr(a, C.c_uint8), a.size, None), "emat_fasta_frame_memory")
+        return self.fasta_records()
+
+    def load_fasta(self, path_or_bytes, ref=None, chunk_rows: int = 0) -> "TipDescs":
+        """An aligned FASTA (a path, or its text as bytes) to tip descriptors, ready for build_usher_like / build_default after
+        set_ref_sequence(tips.ref): the rows that are valid and dated, in input order, with `names`, the reference sequence `ref` (the one
+        given, or the consensus of the valid rows), `report` (emat_fasta_report) and `alignment` (the per-row read-outs)."""
+        ref_c = None if ref is None else np.ascontiguousarray(ref, np.uint8)
+        ref_p = None if ref_c is None else _ptr(ref_c, C.c_uint8)
+        rep = _FastaReportC()
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(path_or_bytes, np.uint8)
+            self._ck(self._lib.emat_fasta_load_memory(self._h, _ptr(a, C.c_uint8), a.size, ref_p, chunk_rows, C.byref(rep)), "emat_fasta_load_memory")
+        else:
+            self._ck(self._lib.emat_fasta_load(self._h, os.fsencode(path_or_bytes), ref_p, chunk_rows, C.byref(rep)), "emat_fasta_load")
+        al = self._align_get(rep.rows)
+        names, _, t_min, t_max, _ = self.fasta_records()
+        is_tip = al.row_status >= 0
+        tips = al.tips
+        tips.t_min = np.ascontiguousarray(t_min[is_tip]); tips.t_max = np.ascontiguousarray(t_max[is_tip])
+        tips.names = [nm for nm, k in zip(names, is_tip) if k]
+        tips.ref = al.ref; tips.alignment = al
+        tips.report = dict(num_records=rep.num_records, num_dated=rep.num_dated, **al.report)
+        return tips
 
     def main_class_mask(self, num_parts: int) -> np.ndarray:
         """Debugging aid: which resident parts run in the main launch (k_run_moves) rather than in a side class (k_run_moves_side)."""

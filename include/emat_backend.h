@@ -1077,6 +1077,82 @@ emat_status emat_tree_built_get(emat_backend* h, emat_flat_tree* out);
 emat_status emat_tree_build_default(emat_backend* h, const emat_tip_descs* tips, uint64_t seed, int32_t* report /*[4]*/);
 emat_status emat_tree_built_ref(emat_backend* h, uint8_t* ref_sequence /*[num_sites]*/);
 
+/* ---- aligned sequences in: consensus, tip deltas and missing runs on the device ----------------------------------------------
+ * replaces: what the reference does with the rows of an aligned FASTA once read_fasta (core/io.cpp:14-97) has framed them -- coding each
+ * character (to_seq_letter / is_valid_seq_letter, core/sequence.h:77-153), deduce_consensus_sequence (core/sequence_utils.h:44-80) and, per
+ * tip, calculate_delta_from_reference (core/sequence_utils.cpp:30-64), in the order of fasta_to_maple (core/cmdline.cpp:26-85).  The framing
+ * itself and the dates in the ids are the host's (include/emat_host.h: emat_fasta_load, emat_seq_id_date_range).
+ * A store on the handle keeps the rows as 4-bit codes (Seq_letters' bit sets, core/sequence.h:21-29), two sites a byte, each row starting on
+ * a byte, beside int32 counts[L][4] of the unambiguous states seen at every site.  L is the handle's num_sites.  Everything is queued on
+ * the engine's stream; all arithmetic is on integers, so the results do not depend on how the rows were cut into calls.
+ * A handle without a device gets EMAT_ERR_NO_DEVICE: there is no CPU path.
+ *
+ *   emat_align_begin       binds the store to `max_rows` rows: max_rows x ceil(L/2) bytes, 8 bytes a row of status, and the counts.  What it held
+ *                          is released first.  hipMemGetInfo is asked: more than is free is EMAT_ERR_CAPACITY with the sizes in emat_last_error.
+ *                          max_rows = 0 releases the room (and is no error on a store never bound).
+ *   emat_align_row_buffer  one of two page-locked buffers of the handle (which = 0 / 1) of at least `bytes` bytes, for rows on their way to
+ *                          emat_align_push_rows: a push from inside one returns while the copy is in flight, and asking for the same buffer
+ *                          again waits for that copy.  Rows pushed from any other memory are read before the push returns.
+ *   emat_align_push_rows   num_rows rows of L ASCII characters, row r at chars + r x row_stride, as a FASTA reader holds them after dropping
+ *                          line ends.  Every character is coded (case-insensitive, U = T, N - ? . all N) and packed; a row with a character
+ *                          that is no sequence letter is INVALID, and the smallest such site and its byte are kept.  The chunk's valid rows
+ *                          are added to the counts.  More rows than reserved is EMAT_ERR_CAPACITY: nothing is pushed.
+ *   emat_align_finish      the reference sequence is given_ref ([L] of 0..3), or with NULL the consensus: per site the state with the largest
+ *                          count, ties to A, then C, then G, then T, an all-zero site A.  Undated rows DO count towards it, invalid rows
+ *                          do not (read_fasta drops the invalid rows, fasta_to_maple forms the consensus and only then drops the undated).
+ *                          The tips are the rows that are valid and dated (row_dated[r] != 0; NULL: every row is dated), in input order.
+ *                          For every tip against the reference sequence: (site, to) at every unambiguous site whose state differs, sites
+ *                          ascending; the maximal runs of ambiguous codes as [start, end) -- sorted, disjoint, non-adjacent, as emat_tip_descs
+ *                          wants them; `R` next to `N` is ONE run -- and how many ambiguous codes were not N (the reference's
+ *                          Ambiguity_precision_loss warnings, counted).  More than INT32_MAX deltas or intervals in all is EMAT_ERR_CAPACITY
+ *                          (the CSR offsets of emat_tip_descs are int32).  Fewer than two tips is no error here: the builders refuse that.
+ *                          More rows may be pushed afterwards and finish called again.  `out` may be NULL.
+ *   emat_align_sizes       the last finish's report
+ *   emat_align_get         its arrays; any pointer may be NULL.  The descriptor arrays also stay in HBM: a later change may hand them to
+ *                          emat_tree_build_usher_like without the round trip through the host.
+ *   emat_align_attach      ties a record of the caller's to the store (the FASTA loader's names and dates): `destroy` is called on it when
+ *                          another is attached, at the next emat_align_begin and when the handle goes.  Works without a device, as do
+ *                          emat_align_num_sites (the handle's L) and emat_align_refuse, with which a layer above the boundary leaves its
+ *                          own refusal in emat_last_error (it returns `status`).
+ *
+ * EMAT_ERR_STATE: push or finish before emat_align_begin; emat_align_sizes / emat_align_get before a finish that succeeded (or after a
+ * push since).  EMAT_ERR_INVALID_ARGUMENT (text in emat_last_error): max_rows < 0, num_rows < 0, row_stride < L, chars NULL with rows
+ * to push, a given_ref entry above 3 (the text names the site).  EMAT_ERR_CAPACITY besides the above: so many rows in one push that the
+ * launch would exceed 2^31 workgroups.  After any refusal the next call works. */
+typedef struct emat_align_report {
+  int64_t num_rows;             /* rows pushed */
+  int32_t num_tips;             /* valid and dated */
+  int32_t num_invalid;          /* rows holding a character that is no sequence letter */
+  int32_t num_undated;          /* valid rows with row_dated[r] == 0 */
+  int64_t num_deltas;           /* over all tips */
+  int64_t num_intervals;
+  int64_t num_precision_loss;   /* ambiguous codes other than N, over all tips */
+} emat_align_report;
+typedef struct emat_align_arrays {
+  int32_t* delta_offset;        /* [num_tips + 1]: these six are the arrays of an emat_tip_descs (t_min / t_max are the host's) */
+  int32_t* delta_site;          /* [num_deltas] */
+  uint8_t* delta_to;            /* [num_deltas] */
+  int32_t* miss_offset;         /* [num_tips + 1] */
+  int32_t* miss_start;          /* [num_intervals] */
+  int32_t* miss_end;            /* [num_intervals] */
+  uint8_t* ref_sequence;        /* [L] given_ref, or the consensus */
+  int32_t* counts;              /* [L][4] */
+  int32_t* row_status;          /* [num_rows] tip index, or -1 undated, or -2 invalid */
+  int32_t* row_bad_site;        /* [num_rows] the first site that holds no sequence letter, -1 in a valid row */
+  uint8_t* row_bad_byte;        /* [num_rows] ... and the byte found there */
+  int32_t* row_precision_loss;  /* [num_rows] ambiguous codes other than N (0 in a row that is no tip: the reference looks at tips only) */
+} emat_align_arrays;
+emat_status emat_align_begin(emat_backend* h, int64_t max_rows);
+emat_status emat_align_row_buffer(emat_backend* h, int32_t which, int64_t bytes, uint8_t** buffer);
+emat_status emat_align_push_rows(emat_backend* h, int32_t num_rows, const uint8_t* chars, int64_t row_stride);
+emat_status emat_align_finish(emat_backend* h, const uint8_t* given_ref /* [L] of 0..3, or NULL */, const uint8_t* row_dated /* [rows], or NULL = all */, emat_align_report* out);
+emat_status emat_align_sizes(emat_backend* h, emat_align_report* out);
+emat_status emat_align_get(emat_backend* h, const emat_align_arrays* out);
+emat_status emat_align_attach(emat_backend* h, void* record, void (*destroy)(void*));
+void* emat_align_attached(const emat_backend* h);
+int32_t emat_align_num_sites(const emat_backend* h);
+emat_status emat_align_refuse(emat_backend* h, emat_status status, const char* text);
+
 /* Byte breakdown of one part's slab as the backend lays it out (works on host-only handles too): header, node records, coalescent
  * cell table, trace ring, list-heap content, list-heap capacity, scratch, and the number of cells kept. */
 emat_status emat_debug_slab_layout(emat_backend* h, int32_t part_id, uint32_t* out8);

@@ -310,6 +310,46 @@ emat_status emat_run_tree_sizes(emat_run* r, int32_t* num_nodes, int32_t* num_mu
 emat_status emat_run_tree_get(emat_run* r, emat_flat_tree* out, uint8_t* ref_sequence /*[L]*/);
 emat_status emat_run_t_max_tip(emat_run* r, double* t_max_tip);
 
+/* ---- aligned FASTA in ------------------------------------------------------------------------------------------------------------
+ * replaces: read_fasta (reference core/io.cpp:14-97) and the host's share of fasta_to_maple (core/cmdline.cpp:26-85); the rows themselves go
+ * through the alignment store of the backend (include/emat_backend.h: emat_align_*), which forms the consensus and every tip's descriptors.
+ *
+ *   emat_seq_id_date_range   extract_date_range_from_sequence_id (core/sequence_utils.cpp:98-211): the date is a suffix of the id after '|' or
+ *                            '-', in the forms YYYY-MM-DD/YYYY-MM-DD, YYYY-MM-DD, YYYY-MM, YYYY, tried in that order; times are days since
+ *                            2020-01-01 (core/dates.cpp:12-46); a month or a year gives [its first day, the first day of the next].  *ok = 0
+ *                            and EMAT_OK for an id without a date.  A month outside 1-12 or a day that the month does not have is no date:
+ *                            the reference leaves such strings to absl::ParseCivilTime, and this one case is NOT verified against it.
+ *   emat_fasta_frame_memory  frames the records of a text as read_fasta does -- empty lines and lines that begin with ';' are skipped; the id is
+ *                            everything after '>' without the white space at its two ends (spaces inside belong to it); white space inside
+ *                            sequence lines is skipped, a '\r' before the line end included; data before the first '>' is a record named "" --
+ *                            and leaves their names, lengths and dates on the handle.  Needs no device.
+ *   emat_fasta_load_memory   frames the text into one of two page-locked row buffers of `chunk_rows` rows (0: about 32 MB) while the other is on
+ *                            its way through emat_align_push_rows, then calls emat_align_finish with given_ref ([L] of 0..3, or NULL for the
+ *                            consensus) and row_dated from the ids.  It leaves on the handle the names, t_min / t_max as floats and the report;
+ *                            the descriptors are the store's (emat_align_get).  On a handle without a device it frames the text, leaves that,
+ *                            and returns EMAT_ERR_NO_DEVICE.
+ *   emat_fasta_load          the same of a file (mapped, not gzip).  EMAT_ERR_IO when it cannot be opened or mapped.
+ *   emat_fasta_sizes / _get  what the last of the three left: per record its name (NUL-terminated, back to back, names_bytes in all), the
+ *                            number of its characters, t_min / t_max (NaN without a date) and whether it has a date; any pointer may be NULL.
+ *
+ * EMAT_ERR_INVALID_ARGUMENT (text in emat_last_error): a text without records ("Input has no sequences!"); a record whose length is not the
+ * handle's L -- the text names it and the first record with their lengths, as fasta_to_maple's does.  The reference stops reading a record
+ * at its first character that is no sequence letter and drops it whatever its length; here such a record must still have L characters,
+ * and is then reported as invalid by the store.  EMAT_ERR_STATE: emat_fasta_sizes / emat_fasta_get before any of the three.  After any refusal
+ * the next call works (the store is released). */
+typedef struct emat_fasta_report {
+  int32_t num_records;      /* framed */
+  int32_t num_dated;        /* ... whose id ends in a date */
+  int64_t names_bytes;      /* of all names with their NULs */
+  emat_align_report rows;   /* emat_align_finish's (zeros after emat_fasta_frame_memory) */
+} emat_fasta_report;
+emat_status emat_seq_id_date_range(const char* id, double* t_min, double* t_max, int32_t* ok);
+emat_status emat_fasta_frame_memory(emat_backend* h, const uint8_t* text, int64_t len, emat_fasta_report* out /* may be NULL */);
+emat_status emat_fasta_load_memory(emat_backend* h, const uint8_t* text, int64_t len, const uint8_t* given_ref, int32_t chunk_rows, emat_fasta_report* out /* may be NULL */);
+emat_status emat_fasta_load(emat_backend* h, const char* path, const uint8_t* given_ref, int32_t chunk_rows, emat_fasta_report* out /* may be NULL */);
+emat_status emat_fasta_sizes(emat_backend* h, emat_fasta_report* out);
+emat_status emat_fasta_get(emat_backend* h, char* names, int64_t* lengths, float* t_min, float* t_max, uint8_t* dated);
+
 #ifdef __cplusplus
 }
 #endif
