@@ -14,6 +14,8 @@ from .engine import (  # noqa: F401
     ExpPopMovesResult,
     ExpPopSpec,
     FlatTree,
+    MccMutationSupport,
+    MccNodeTimes,
     MccTree,
     MpoxMovesResult,
     MpoxSpec,

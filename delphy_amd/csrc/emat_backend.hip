@@ -34,6 +34,7 @@
 #include "emat_build.hpp"           // initial-tree construction: the graft loop as a kernel, the finishing passes on the host
 #include "emat_probe_kernels.hpp"   // the tree probers, one family for the resident tree and the kept samples: lineage and site-state prevalence over time
 #include "emat_mcc_kernels.hpp"     // sampled trees kept in HBM, and the maximum-clade-credibility tree derived from them
+#include "emat_mcc_summary_kernels.hpp"   // on the MCC tree: the spread of every node's date over the samples, and the support of the master's mutations
 #include "emat_site_rate_kernels.hpp"   // the site-rate moves: steps on alpha and the Gibbs draw of every nu_l
 #include "emat_skygrid_kernels.hpp"     // the Skygrid population moves: tau, the zero mode and the HMC on the gammas
 #include "emat_exp_pop_kernels.hpp"     // the Exponential population moves: n0 and the growth rate
@@ -97,6 +98,7 @@ emat_status emat_set_option(emat_backend* h, const char* key, const char* value)
   if (strcmp(key, "debug_fail_gather") == 0) { h->cfg_debug_fail_gather = atoi(value) != 0; return EMAT_OK; }   // (a test hook that is armed in the middle of a run)
   if (strcmp(key, "mcc_table_log2") == 0) { h->cfg_mcc_table_log2 = std::max(0, std::min(32, atoi(value))); return EMAT_OK; }   // (read by every emat_mcc_derive)
   if (strcmp(key, "samples_probe_chunk") == 0) { h->cfg_samples_probe_chunk = std::max(0, atoi(value)); return EMAT_OK; }   // (read by every emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors)
+  if (strcmp(key, "mcc_summary_chunk") == 0) { h->cfg_mcc_summary_chunk = std::max(0, atoi(value)); return EMAT_OK; }   // (read by every emat_mcc_node_times)
   if (h->slabs_on_device) return fail(h, EMAT_ERR_STATE, "emat_set_option: options are set before the first launch");
   const std::string k(key);
   const char* e = value;
@@ -653,6 +655,7 @@ emat_status emat_last_run_ms(emat_backend* h, double* ms) {
 #include "emat_mcc_host.hpp"
 #include "emat_probe_host.hpp"          // the probers' driver and the resident tree's entry points
 #include "emat_samples_probe_host.hpp"  // the store's entry points
+#include "emat_mcc_summary_host.hpp"    // node-age spreads and mutation support on the last derivation
 #include "emat_build_host.hpp"
 #include "emat_utree_host.hpp"
 #include "emat_site_rate_host.hpp"

@@ -28,7 +28,7 @@ emat_status mcc_store_alloc(emat_backend* h, const std::string& w, int64_t capac
   const size_t store_bytes = nodes * k_mcc_store_bytes_per_node + (size_t)capacity * 4, derive_bytes = nodes * k_mcc_derive_bytes_per_node + (size_t)n * 64;
   if (nodes > X.parent.n || (size_t)capacity > X.root.n) {
     HIP_TRY(hipStreamSynchronize(h->stream));
-    X.release(); h->probe.release_samples();
+    X.release(); h->probe.release_samples(); h->mcs.release();
     emat_status st = mcc_check_room(h, w, store_bytes + derive_bytes, std::to_string(capacity) + " samples of " + std::to_string(n) + " nodes (" + mcc_mb(store_bytes) + " for the store, " + mcc_mb(derive_bytes) + " for a derivation over all of them)");
     if (st) return st;
     HIP_TRY(X.parent.alloc(nodes)); HIP_TRY(X.c0.alloc(nodes)); HIP_TRY(X.c1.alloc(nodes)); HIP_TRY(X.t.alloc(nodes)); HIP_TRY(X.root.alloc((size_t)capacity));
@@ -421,7 +421,7 @@ emat_status emat_mcc_derive(emat_backend* h, int32_t first, int32_t count, int32
   if (out->t_mrca) HIP_TRY(hipMemcpy(out->t_mrca, X.t_mrca.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   if (out->num_exact) HIP_TRY(hipMemcpy(out->num_exact, X.num_exact.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   out->num_distinct_clades = info[1] + (info[2] > 0 ? 1 : 0); out->table_slots = (int64_t)X.table.mask + 1; out->table_regrows = X.table_regrows;
-  X.derived_M = M; X.derived_n = n; X.derived_first = first; X.derived_stride = stride;
+  X.derived_M = M; X.derived_n = n; X.derived_first = first; X.derived_stride = stride; X.derived_master = master;
   return EMAT_OK;
 }
 

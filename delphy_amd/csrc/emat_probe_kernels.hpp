@@ -310,25 +310,30 @@ __global__ void __launch_bounds__(256) k_probe_mean(const double* p_all, int cou
   for (int k = 1; k < count; ++k) s += p_all[(size_t)k * values + i];
   mean[i] = s / count;
 }
+// The bitonic network every sort over the samples goes through (the order statistics below, the MCC nodes' dates in emat_mcc_summary_kernels.hpp):
+// the `padded` (a power of two) doubles of `sorted`, in LDS and complete (a __syncthreads behind their last write), ascending; called by the whole workgroup.
+__device__ inline void probe_bitonic_sort(double* sorted, int padded) {
+  for (int size = 2; size <= padded; size *= 2) {
+    for (int gap = size / 2; gap > 0; gap /= 2) {
+      for (int k = threadIdx.x; k < padded; k += blockDim.x) {
+        const int partner = k ^ gap;
+        if (partner > k) {
+          const double a = sorted[k], b = sorted[partner];
+          const bool ascending = (k & size) == 0;
+          if ((a > b) == ascending) { sorted[k] = b; sorted[partner] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
 // `padded`: the power of two >= count (<= k_probe_sort_max); dynamic LDS: padded doubles.  order_stats [num_ranks][values].
 __global__ void __launch_bounds__(k_probe_sort_threads) k_probe_order_stats(const double* p_all, int count, int padded, size_t values, const int32_t* ranks, int num_ranks, double* order_stats) {
   extern __shared__ __attribute__((aligned(16))) double probe_sorted[];
   for (size_t i = blockIdx.x; i < values; i += gridDim.x) {   // (uniform over the workgroup)
     for (int k = threadIdx.x; k < padded; k += blockDim.x) probe_sorted[k] = k < count ? p_all[(size_t)k * values + i] : __builtin_inf();
     __syncthreads();
-    for (int size = 2; size <= padded; size *= 2) {
-      for (int gap = size / 2; gap > 0; gap /= 2) {
-        for (int k = threadIdx.x; k < padded; k += blockDim.x) {
-          const int partner = k ^ gap;
-          if (partner > k) {
-            const double a = probe_sorted[k], b = probe_sorted[partner];
-            const bool ascending = (k & size) == 0;
-            if ((a > b) == ascending) { probe_sorted[k] = b; probe_sorted[partner] = a; }
-          }
-        }
-        __syncthreads();
-      }
-    }
+    probe_bitonic_sort(probe_sorted, padded);
     for (int r = threadIdx.x; r < num_ranks; r += blockDim.x) {
       const int32_t q = ranks[r];
       if (q >= 0 && q < count) order_stats[(size_t)r * values + i] = probe_sorted[q];

@@ -217,6 +217,7 @@ struct MccHost {
   MccTable table{}; int32_t table_regrows = 0; int table_log2_hint = 0;   // the table of clade counts of the last derivation; the size it ended with is where the next one starts
   int32_t derived_M = 0, derived_n = 0;                // the (M x n) correspondence table of the last derivation is valid
   int32_t derived_first = 0, derived_stride = 1;       // ... and belongs to the samples derived_first + k * derived_stride (emat_mcc_probe_ancestors probes those)
+  int32_t derived_master = 0;                          // ... of which this one (a position, not a slot) is the master (emat_mcc_mutation_support reads its mutations)
   // Opt-in (emat_tree_samples_reserve_mutations): what a slot keeps of its mutations, for the site-state prober over samples.  Per slot
   // the per-node list headers and the reference sequence; the records of all slots in one arena, a slot's in one segment handed out
   // here on the host (mut_base / mut_len; base -1: the sample came without mutations).  The headers' offsets are relative to the segment.
@@ -227,6 +228,17 @@ struct MccHost {
   template <class T> static void drop(DevBuf<T>& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 0; }
   void release_mutations() { drop(mut_hdr); drop(mut_ref); drop(mut_arena); mut_capacity = 0; mut_used = 0; mut_L = 0; mut_slots = 0; mut_n = 0; mut_base.clear(); mut_len.clear(); }
   void release() { drop(parent); drop(c0); drop(c1); drop(root); drop(t); drop(fp); drop(keys); drop(ntips); drop(arrive); drop(corr); drop(counts); drop(hist); drop(exact); release_mutations(); capacity = 0; count = 0; derived_M = 0; table_log2_hint = 0; }
+};
+
+// What emat_mcc_node_times and emat_mcc_mutation_support work in (emat_mcc_summary_kernels.hpp, emat_mcc_summary_host.hpp): the chunk's
+// (M x B) times and flags, the call's outputs and what it uploads.  Grow-only; released with the store, which sizes the largest of it.
+struct MccSummaryScratch {
+  DevBuf<double> x, quantiles, q_exact, q_mrca, hpd_exact, hpd_mrca, mean_t, t_min, t_max;
+  DevBuf<uint8_t> e;
+  DevBuf<int32_t> flags, nodes, num_exact, rec_offset, num_with;
+  DevBuf<long long> seg_base; DevBuf<uint32_t> seg_len;
+  template <class T> static void drop(DevBuf<T>& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 0; }
+  void release() { drop(x); drop(e); drop(q_exact); drop(q_mrca); drop(hpd_exact); drop(hpd_mrca); drop(num_exact); drop(nodes); drop(rec_offset); drop(num_with); drop(mean_t); drop(t_min); drop(t_max); }
 };
 
 // The alignment store and what emat_align_finish works in (emat_align_kernels.hpp, emat_align_host.hpp).  The store is sized by emat_align_begin, exactly;
@@ -351,7 +363,9 @@ struct emat_backend {
   SubstScratch sb;                  // what emat_subst_moves works in
   MpoxScratch mx;                   // what emat_mpox_moves works in
   MccHost mcc;                      // the sampled trees kept in HBM (emat_tree_sample_*) and what emat_mcc_derive works in
+  MccSummaryScratch mcs;            // what emat_mcc_node_times and emat_mcc_mutation_support work in
   AlignHost al;                     // the aligned rows kept in HBM (emat_align_*) and the tip descriptors made from them
+  int cfg_mcc_summary_chunk = 0;    // "mcc_summary_chunk" (testing aid): MCC nodes emat_mcc_node_times works on at a time (0: as many as half the free memory holds)
   int cfg_samples_probe_chunk = 0;  // "samples_probe_chunk" (testing aid): samples the batched probers (emat_tree_samples_probe_ancestors, emat_tree_samples_probe_site_states) work on at a time (0: as many as half the free memory holds)
   int cfg_mcc_table_log2 = 0;       // "mcc_table_log2" (testing aid): log2 of the slots the table of clade counts starts with (0: four per node), so that its growth runs
   BuiltTree built;                  // what emat_tree_build_usher_like made, until it is fetched (emat_tree_built_get)

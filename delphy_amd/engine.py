@@ -90,6 +90,12 @@ class _SamplesProbeResultC(C.Structure):
                 ("order_stats", C.POINTER(C.c_double)), ("cells_to_skip", C.POINTER(C.c_int32))]
 
 
+class _MccNodeTimesResultC(C.Structure):
+    _fields_ = [("num_quantiles", C.c_int32), ("quantiles", C.POINTER(C.c_double)), ("hpd_mass", C.c_double),
+                ("q_exact", C.POINTER(C.c_double)), ("q_mrca", C.POINTER(C.c_double)), ("hpd_exact", C.POINTER(C.c_double)), ("hpd_mrca", C.POINTER(C.c_double)),
+                ("num_exact", C.POINTER(C.c_int32)), ("times", C.POINTER(C.c_double)), ("is_exact", C.POINTER(C.c_uint8))]
+
+
 class _SiteRateStepC(C.Structure):
     _fields_ = [("proposed_alpha", C.c_double), ("log_p_proposed", C.c_double), ("log_metropolis", C.c_double), ("u", C.c_double), ("accepted", C.c_int32), ("pad_", C.c_int32)]
 
@@ -424,6 +430,31 @@ class MccTree:
     table_slots: int
 
 
+@dataclass
+class MccNodeTimes:
+    """What emat_mcc_node_times returns (include/emat_backend.h: emat_mcc_node_times_result): per node asked for, over the samples of the
+    last derivation.  `exact`: the samples that have the node's clade; `mrca`: all of them."""
+    nodes: np.ndarray                  # [nodes] the MCC nodes answered, as asked for
+    quantiles: np.ndarray              # [q] as asked for
+    hpd_mass: float
+    num_exact: np.ndarray              # [nodes] samples that have the node's clade
+    q_exact: Optional[np.ndarray]      # [q][nodes], or None without quantiles
+    q_mrca: Optional[np.ndarray]
+    hpd_exact: Optional[np.ndarray]    # [2][nodes]: lo, hi of the shortest interval holding hpd_mass of the values, or None with hpd_mass 0
+    hpd_mrca: Optional[np.ndarray]
+    times: Optional[np.ndarray]        # [nodes][count] the corresponding node's time in every sample, in sample order, or None unless per_sample
+    is_exact: Optional[np.ndarray]     # [nodes][count] bool
+
+
+@dataclass
+class MccMutationSupport:
+    """What emat_mcc_mutation_support returns: per mutation of the master, in the order tree_sample_get_mutations(master slot) lists them."""
+    num_with: np.ndarray               # [records] samples that have the node's clade and the mutation on its branch
+    mean_t: np.ndarray                 # [records] mean time of the mutation over those samples, summed in sample order
+    t_min: np.ndarray                  # [records] its earliest ...
+    t_max: np.ndarray                  # ... and latest time
+
+
 class _TipDescsC(C.Structure):
     _fields_ = [("num_tips", C.c_int32), ("t_min", C.POINTER(C.c_float)), ("t_max", C.POINTER(C.c_float)),
                 ("delta_offset", C.POINTER(C.c_int32)), ("delta_site", C.POINTER(C.c_int32)), ("delta_to", C.POINTER(C.c_uint8)),
@@ -700,6 +731,7 @@ def load_library():
         "emat_tree_samples_mutation_info": [B, P(i64), P(i64), P(i32)],
         "emat_tree_samples_probe_site_states": [B, P(_PopModelC), i32, i32, i32, i32, i32, P(i32), dbl, dbl, i32, P(_SamplesProbeResultC)],
         "emat_mcc_probe_site_states": [B, P(_PopModelC), i32, i32, P(i32), dbl, dbl, i32, P(_SamplesProbeResultC)],
+        "emat_mcc_node_times": [B, i32, P(i32), P(_MccNodeTimesResultC)], "emat_mcc_mutation_support": [B, i64, P(i64), P(i32), P(dbl), P(dbl), P(dbl)],
         "emat_run_note_device_reassembled": [R, i32, P(i32), P(C.c_uint8)], "emat_run_set_paranoid": [R, i32], "emat_run_set_reference_remainder": [R, i32],
         "emat_site_rate_moves": [B, P(dbl), P(i32), dbl, i32, u64, P(_SiteRateResultC)], "emat_get_nu_l": [B, P(dbl)], "emat_debug_sample_gamma": [B, u64, i32, dbl, dbl, P(dbl)],
         "emat_skygrid_moves": [B, P(_PopModelC), P(_SkygridSpecC), dbl, dbl, i32, i32, P(dbl), i32, P(dbl), u64, P(_SkygridResultC)],
@@ -1195,6 +1227,42 @@ class EmatBackend:
         self._ck(self._lib.emat_mcc_get_derivation(self._h, None, C.byref(count), None), "emat_mcc_get_derivation")
         return self._samples_probe(lambda pc, npc, res: self._lib.emat_mcc_probe_ancestors(self._h, pc, npc, int(mk.shape[0]), _ptr(mk, C.c_int32) if mk.size else None, t_start, t_end, num_t_cells, res),
                                    "emat_mcc_probe_ancestors", pops, int(count.value), int(mk.shape[0]), num_t_cells, ranks, per_sample, mean)
+
+    # ---- on the MCC tree: node-date spreads and the support of the master's mutations (include/emat_backend.h) ----
+    def mcc_node_times(self, nodes=None, quantiles=(), hpd_mass: float = 0.0, per_sample: bool = False) -> "MccNodeTimes":
+        """Over the samples of the last mcc_derive, for every MCC node of `nodes` (None: all, in node order): quantiles and the shortest interval
+        holding `hpd_mass` of the node's dates, over the samples that have its clade (`exact`) and over all (`mrca`); with `per_sample` the dates themselves."""
+        n = self.tree_samples_info()[2]
+        count = C.c_int32(0)
+        self._ck(self._lib.emat_mcc_get_derivation(self._h, None, C.byref(count), None), "emat_mcc_get_derivation")
+        m = max(int(count.value), 1)
+        nd = None if nodes is None else np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        cols = max(n, 1) if nd is None else max(int(nd.shape[0]), 1)
+        q = np.ascontiguousarray(quantiles, np.float64).reshape(-1)
+        nq, hpd = int(q.shape[0]), float(hpd_mass) != 0.0
+        r = MccNodeTimes(np.arange(n, dtype=np.int32) if nd is None else nd, q, float(hpd_mass), np.zeros(cols, np.int32),
+                         np.zeros((nq, cols)) if nq else None, np.zeros((nq, cols)) if nq else None, np.zeros((2, cols)) if hpd else None, np.zeros((2, cols)) if hpd else None,
+                         np.zeros((cols, m)) if per_sample else None, np.zeros((cols, m), np.uint8) if per_sample else None)
+        opt = lambda a, ct: None if a is None else _ptr(a, ct)
+        c = _MccNodeTimesResultC(nq, _ptr(q, C.c_double) if nq else None, float(hpd_mass), opt(r.q_exact, C.c_double), opt(r.q_mrca, C.c_double), opt(r.hpd_exact, C.c_double), opt(r.hpd_mrca, C.c_double),
+                                 _ptr(r.num_exact, C.c_int32), opt(r.times, C.c_double), opt(r.is_exact, C.c_uint8))
+        self._ck(self._lib.emat_mcc_node_times(self._h, 0 if nd is None else int(nd.shape[0]), None if nd is None else (_ptr(nd, C.c_int32) if nd.size else _ptr(np.zeros(1, np.int32), C.c_int32)), C.byref(c)),
+                 "emat_mcc_node_times")
+        if per_sample:
+            r.is_exact = r.is_exact.astype(bool)
+        return r
+
+    def mcc_mutation_support(self) -> "MccMutationSupport":
+        """For every mutation of the last mcc_derive's master, in the order tree_sample_get_mutations(master slot) lists them: how many samples have
+        the node's clade and the mutation on its branch, and the mean, earliest and latest of its times over those."""
+        nm = C.c_int64(0)
+        self._ck(self._lib.emat_mcc_mutation_support(self._h, 0, C.byref(nm), None, None, None, None), "emat_mcc_mutation_support")
+        k = int(nm.value)
+        r = MccMutationSupport(np.zeros(k, np.int32), np.zeros(k), np.zeros(k), np.zeros(k))
+        if k:
+            self._ck(self._lib.emat_mcc_mutation_support(self._h, k, C.byref(nm), _ptr(r.num_with, C.c_int32), _ptr(r.mean_t, C.c_double), _ptr(r.t_min, C.c_double), _ptr(r.t_max, C.c_double)),
+                     "emat_mcc_mutation_support")
+        return r
 
     # ---- samples that keep their mutations, and the site-state prober over them (include/emat_backend.h) ----
     def tree_samples_reserve_mutations(self, mutation_records: int) -> None:

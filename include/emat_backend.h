@@ -121,6 +121,7 @@ emat_status emat_backend_destroy(emat_backend* h);
  *   "debug_fail_gather" (1: the next deferred gather of the device-resident tree reports an inconsistency; may be set at any time);
  *   "mcc_table_log2" (log2 of the slots emat_mcc_derive's table of clade counts starts with, 0 = four per node: a small value makes it grow; may be set at any time);
  *   "samples_probe_chunk" (samples emat_tree_samples_probe_ancestors / emat_mcc_probe_ancestors and the site-state forms work on at a time, 0 = as many as fit: results do not depend on it; may be set at any time);
+ *   "mcc_summary_chunk" (MCC nodes emat_mcc_node_times works on at a time, 0 = as many as fit: results do not depend on it; may be set at any time);
  *   profiling builds: "fn_min_lists", "phase_extra". */
 emat_status emat_set_option(emat_backend* h, const char* key, const char* value);
 /* Size of the library's host thread pool (per process, before its first parallel loop; 0 = default: min(cores, 16)). */
@@ -479,6 +480,69 @@ emat_status emat_tree_samples_probe_site_states(emat_backend* h,
 emat_status emat_mcc_probe_site_states(emat_backend* h, const emat_pop_model* pop_models, int32_t num_pop_models,
     int32_t num_sites, const int32_t* sites /* [num_sites] */,
     double t_start, double t_end, int32_t num_t_cells, emat_samples_probe_result* out);
+/* ---- on the MCC tree: the spread of every node's date over the samples, and the support of the master's mutations -------------
+ * A time tree is drawn with a bar on every node (the spread of that node's date over the samples) and with its mutations marked by
+ * how many samples agree with them.  The reference exposes the MCC tree's base trees and, per base tree, the corresponding node
+ * and whether it matches exactly (core/mcc_tree.h:91-98), and exports both (tools/delphy_wasm.cpp:1503-1523) so that a front end
+ * loops over every base tree.  Here that loop would pull the (M x n) correspondence table and every sample to the host; the two
+ * calls below make those numbers where the table, the samples' times and their mutation lists already lie.
+ *
+ * Both work on the LAST VALID DERIVATION: its first / count / stride, its master and its correspondence table, as
+ * emat_mcc_probe_ancestors uses them.  M = its sample count, sample k = slot first + k * stride, n = nodes per sample; for MCC node
+ * v, c(k, v) = corr[k][v] and x(k, v) = the double t[c(k, v)] of sample k as the store holds it.  Both touch only the store, may be
+ * called while the parts are out, and queue on the engine's stream; with several processes rank 0 answers alone; a handle without
+ * a device gets EMAT_ERR_NO_DEVICE.  No other call's behaviour or bits change.
+ *
+ *   emat_mcc_node_times   for each node asked for (mcc_nodes NULL: all n in node order, num_nodes is ignored; a node may be given
+ *     twice, every entry is answered; tips are nodes like any other) and each of two sets of samples --
+ *       mrca:   all k, m = M (the spread behind emat_mcc_derive's t_mrca);
+ *       exact:  {k : exact[k][v]}, m = num_exact[v] >= 1 (the master matches itself; the spread behind t) --
+ *     with s = the set's m values x(k, v) sorted ascending:
+ *       quantile j   s[floor(quantiles[j] * (double)(m - 1))]: one double multiplication and one floor
+ *       hpd          w = min(m, max(1, ceil(hpd_mass * (double)m))); i* = the SMALLEST i in [0, m - w] that minimises the double
+ *                    s[i + w - 1] - s[i]; lo = s[i*], hi = s[i* + w - 1]: the shortest interval holding that share of the values,
+ *                    the first one on ties
+ *       times / is_exact   x(k, v) and exact[k][v] themselves, [num_nodes][M] in sample order: for the handful of nodes whose
+ *                    histogram is drawn; num_nodes x M above 2^26 values is EMAT_ERR_CAPACITY.
+ *     Every output is one of the doubles in the store: nothing is averaged or interpolated, and the results are the same for
+ *     every chunk size and from call to call.  The sort is the probers' (an exact sort in LDS): a derivation over more than
+ *     4 096 samples is EMAT_ERR_CAPACITY.  The nodes are worked on in chunks sized from half the free device memory (9 bytes per
+ *     node and sample); option "mcc_summary_chunk" (0 = automatic; may be set at any time) forces a chunk of that many nodes for
+ *     tests.  Only what is asked for crosses to the host.
+ *     EMAT_ERR_STATE: no valid derivation (none yet, emat_tree_samples_clear since, or the last one failed).
+ *     EMAT_ERR_INVALID_ARGUMENT: num_nodes < 1 with a list; a node outside [0, n) (the text names the entry); a quantile outside
+ *     [0, 1] or NaN; hpd_mass outside [0, 1] or NaN; num_quantiles > 0 without quantiles; every output NULL; q_exact / q_mrca
+ *     without quantiles, hpd_exact / hpd_mrca with hpd_mass = 0.  EMAT_ERR_INTERNAL: a node time of a chosen sample that is not
+ *     finite (+inf pads the sort; the text names the sample's position), or a table entry outside the tree.
+ *
+ *   emat_mcc_mutation_support   records are the MASTER sample's mutations in the CSR order emat_tree_sample_get_mutations(master
+ *     slot) returns them: node order, each list in stored order, the root's own list included.  For record j on node v with
+ *     (site, from, to), sample k HAS it when exact[k][v] and the stored list of node c(k, v) in sample k holds a record with the
+ *     same site, from and to; its time in that sample is the t of the FIRST such record in stored order.
+ *       num_with[j]   how many chosen samples have it (>= 1: the master has it)
+ *       mean_t[j]     the sum of those times IN SAMPLE ORDER, divided once by num_with[j]
+ *       t_min / t_max the smallest and largest of those times
+ *     *num_mutations (may be NULL) receives the number of records; with every array NULL that is all the call does.
+ *     EMAT_ERR_STATE: no valid derivation; a store without mutation room; a chosen sample pushed without mutations (the text names
+ *     its position and slot).  EMAT_ERR_CAPACITY, with *num_mutations set: `capacity` (records) too small.  EMAT_ERR_INTERNAL: a list
+ *     outside its segment.
+ * After any refusal the next call works. */
+typedef struct emat_mcc_node_times_result {
+  int32_t num_quantiles;     /* in: 0, or how many quantiles */
+  const double* quantiles;   /* in: [num_quantiles], each in [0, 1] */
+  double  hpd_mass;          /* in: in (0, 1]; 0: no HPD asked for */
+  double* q_exact;           /* [num_quantiles][num_nodes], or NULL */
+  double* q_mrca;            /* [num_quantiles][num_nodes], or NULL */
+  double* hpd_exact;         /* [2][num_nodes]: lo, hi; or NULL */
+  double* hpd_mrca;          /* [2][num_nodes]: lo, hi; or NULL */
+  int32_t* num_exact;        /* [num_nodes], or NULL */
+  double* times;             /* [num_nodes][M] in sample order, or NULL: x(k, v) itself */
+  uint8_t* is_exact;         /* [num_nodes][M] in sample order, or NULL: exact[k][v] itself */
+} emat_mcc_node_times_result;
+emat_status emat_mcc_node_times(emat_backend* h, int32_t num_nodes, const int32_t* mcc_nodes /* NULL: all n, in node order */,
+    emat_mcc_node_times_result* out);
+emat_status emat_mcc_mutation_support(emat_backend* h, int64_t capacity /* records */, int64_t* num_mutations,
+    int32_t* num_with /* [records] */, double* mean_t, double* t_min, double* t_max /* any may be NULL */);
 /* One run over several processes, one GPU each, EVERY one with the whole tree in its HBM (the tree is a few tens of MB; what
  * is worth sharding is the moves).  Every process cuts the same partition and calls emat_tree_repartition_range with its own
  * block [part_lo, part_hi) of the parts (backend part id = part - part_lo): the sequence states at the cut points and the
