@@ -166,16 +166,22 @@ def run_parity(sc, num_parts, moves_per_part, seed=11, topology=True, only_displ
         gpu.close(); orc.close()
 
 
-def replay_device_parts_in_the_oracle(sc, b, run, ref, moves_total, trace, oracle_parts=None):
+def replay_device_parts_in_the_oracle(sc, b, run, ref, moves_total, trace, oracle_parts=None, evo=None):
     """Hand the oracle exactly what the device starts a pass from -- every part's tree as the kernels cut it, the coalescent
     tables as the kernels built them, the position of every part's random stream -- run the pass on both, compare everything.
-    `oracle_parts`: a list that receives the ORACLE's part trees after the pass (what its own moves made of them)."""
+    `oracle_parts`: a list that receives the ORACLE's part trees after the pass (what its own moves made of them).
+    `evo` = (mu[P], pi[P][4], q[P][4][4], partition_for_site[L]): the model the device holds, where that is not the scenario's HKY."""
     n, root_part = run.num_parts()
     trees = [b.part_download(p) for p in range(n)]
     rngs = [b.part_rng(p) for p in range(n)]
     orc = OracleEngine(sc.num_sites, trace_moves=trace)
     try:
-        orc.set_ref_sequence(ref); orc.set_hky(sc.mu, sc.kappa, sc.pi); orc.set_flags(sc.t_max_tip)
+        orc.set_ref_sequence(ref)
+        if evo is not None:
+            orc.set_evo(evo[0], evo[1], evo[2], np.ones(sc.num_sites), evo[3])
+        else:
+            orc.set_hky(sc.mu, sc.kappa, sc.pi)
+        orc.set_flags(sc.t_max_tip)
         orc.upload_parts(trees, [p == root_part for p in range(n)], [r["key"] for r in rngs])
         for p in range(n):
             tab = b.part_coalescent(p)

@@ -221,7 +221,8 @@ def test_coalescent_posterior_of_n_tips_through_partitioned_cycles_on_the_gpu():
 
 # ---- two tips that DIFFER at m sites ---------------------------------------------------------------------------------
 # Both dated exactly t = 0.  To first order in mu h every differing site contributes a factor proportional to the total
-# branch length 2h (one mutation, somewhere on either branch; by reversibility both placements weigh the same), every other
+# branch length 2h (one mutation, somewhere on either branch; under HKY, which is reversible, pi_a q_ab = pi_b q_ba and both
+# placements weigh the same -- under the APOBEC model's q1 they do not: the model further down), every other
 # site exp(-2 q mu h), the prior exp(-h/N):  h ~ Gamma(m + 1, 1/N + 2 lambda),  E[h] = (m + 1) / rate,  sd = sqrt(m + 1) / rate.
 # What this one reaches that the others do not: explicit mutations -- their times bound the displacement of the root and
 # are re-drawn by branch reforms, they hop between the two branches through the root (the root sequence and with it the
@@ -313,3 +314,133 @@ def test_two_differing_tips_posterior_closed_form_on_the_gpu():
     _check_differing(hs, on_first, ref_changed, _lambda_of(ref))
     hs, on_first, ref_changed, ref = _chain_differing(lambda: d.EmatBackend(L), True, 41)      # whole cycles, tree resident in HBM
     _check_differing(hs, on_first, ref_changed, _lambda_of(ref))
+
+
+# ---- two tips that differ at three sites of the APOBEC model's second partition: which end of the mutation is the root's ----------------
+# Both dated exactly t = 0, flat pi, two site partitions (a fixed random 40 % of the sites in the second), Jukes-Cantor in the first and the APOBEC
+# model's q1 at rho = 0.5 in the second (q_CT = 1/3 + 2 rho, q_TC = 1/3).  At three sites of the second partition tip 1 holds C and tip 2 holds T.
+# q1 is not reversible under the flat pi, so where the one mutation sits says which state the root has: C with the mutation C -> T on the way to tip 2,
+# T with T -> C on the way to tip 1; to first order the root holds C with probability q_CT / (q_CT + q_TC) = 0.8.  A model that ignored the asymmetry
+# would give 0.5, one that read q transposed 0.2.  Exactly, with P(h) = exp(mu Q_beta h) the 4 x 4 transition matrix of a branch of length h:
+#   p(h)  ~  exp(-h / N)  x  prod over identical sites (partition beta, state a) of sum_r pi_r P_ra(h)^2  x  (sum_r pi_r P_rC(h) P_rT(h))^3,
+#   P(root = C at a differing site | h) = pi_C P_CC P_CT / sum_r pi_r P_rC P_rT,
+# integrated here by quadrature.  The share depends on h only at order mu h q: with these numbers the quadrature gives 0.79989 for the share against
+# the first order's 0.8, and between h = 50 and h = 300 it moves from 0.79996 to 0.79975, so the grid's effect on h (3 % of 134) moves it by 4e-6, a
+# thousandth of the standard error below: the share is held to the file's 4 batch-means standard errors and nothing more.
+# The chain goes part by part through configure(..., evo=...), as _chain_differing does with via_run_driver=False: the run driver takes no general model.
+# (30 000 cycles on the oracle, 7 s: the standard error is then 0.0012, and seed 43 stands 1.1 of them from the quadrature; 5 000 on the GPU, as the file's other tests)
+RHO_APOBEC, C_STATE, T_STATE, CYCLES_APOBEC_ORACLE = 0.5, 1, 3, 30000
+
+
+def _apobec_two_tips(seed):
+    """-> (tree, ref, evo, the three differing sites)."""
+    from delphy_amd.engine import mpox_q_matrices
+    rng = np.random.default_rng(seed)
+    ref = rng.integers(0, 4, L).astype(np.uint8)
+    pfs = (rng.random(L) < 0.4).astype(np.int32)
+    sites = np.sort(rng.choice(L, size=M_DIFF, replace=False))
+    pfs[sites] = 1
+    ref[sites] = C_STATE
+    t = d.FlatTree.empty(3, M_DIFF, 0, 0)
+    t.root = 0
+    t.child0[0], t.child1[0] = 1, 2
+    t.parent[1] = t.parent[2] = 0
+    t.t[:] = (-120.0, 0.0, 0.0)
+    t.t_min[:] = (-3.4028234663852886e38, 0.0, 0.0)
+    t.t_max[:] = (3.4028234663852886e38, 0.0, 0.0)
+    t.mut_offset[:] = (0, 0, 0, M_DIFF)               # the root holds C: three mutations C -> T on the branch to node 2, sorted by (t, site)
+    for k in range(M_DIFF):
+        t.mut_site[k], t.mut_from[k], t.mut_to[k], t.mut_t[k] = sites[k], C_STATE, T_STATE, -100.0 + 30.0 * k
+    evo = (np.array([MU, MU]), np.full((2, 4), 0.25), np.stack(mpox_q_matrices(RHO_APOBEC)), pfs)
+    return t, ref, evo, sites
+
+
+def _expm(A):
+    """exp(A) of a small matrix of small norm (mu h |Q| < 0.05 here): the Taylor series to its 24th term."""
+    out, term = np.eye(A.shape[0]), np.eye(A.shape[0])
+    for k in range(1, 25):
+        term = term @ A / k
+        out = out + term
+    return out
+
+
+def _apobec_quadrature(ref, evo, sites):
+    """-> (E[h], the posterior probability that the root holds C at a differing site), by the trapezoid rule on h in (0, 2000] in steps of 1: the
+    density, h^3 exp(-h / 33.5) to first order, is smooth on that scale and has left nothing at 2000 (steps of 1/4 to 4000 give the same 134.0438 and 0.7998873)."""
+    mu, pi, q, pfs = evo
+    same = np.ones(L, bool); same[sites] = False
+    counts = np.zeros((2, 4))
+    np.add.at(counts, (pfs[same], ref[same]), 1.0)
+    hs = np.arange(1, 2001) * 1.0
+    logp, share = np.empty(hs.shape[0]), np.empty(hs.shape[0])
+    for i, h in enumerate(hs):
+        P = [_expm(mu[b] * h * q[b]) for b in range(2)]
+        lp = -h / N_POP
+        for b in range(2):
+            lp += float(counts[b] @ np.log(pi[b] @ (P[b] ** 2)))
+        both = pi[1] * P[1][:, C_STATE] * P[1][:, T_STATE]
+        logp[i] = lp + M_DIFF * math.log(both.sum())
+        share[i] = both[C_STATE] / both.sum()
+    w = np.exp(logp - logp.max())
+    w[-1] *= 0.5                                     # (the density vanishes at h = 0, the other end of the rule)
+    w /= w.sum()
+    return float(w @ hs), float(w @ share)
+
+
+def _chain_apobec(eng, seed, cycles):
+    """-> (root heights, the number of the three sites at which the root holds C, per cycle; ref, evo, sites)."""
+    tree, ref, evo, sites = _apobec_two_tips(seed)
+    sc = Scenario("two tips, APOBEC model", tree, ref, 0.0, MU, KAPPA, PI, d.PopModel.const(N_POP), L)
+    hs, root_C = [], []
+    for c in range(cycles):
+        sc.tree = tree
+        configure(eng, sc, ref, [tree], [True], [seed * 7919 + c], 0, t_step=T_STEP, evo=evo)
+        eng.run_moves_per_part(30)
+        tree = eng.part_download(0)
+        r = int(tree.root)
+        state = {int(l): int(ref[l]) for l in sites}          # the root's sequence: `ref` with the root node's own deltas applied
+        for k in range(int(tree.mut_offset[r]), int(tree.mut_offset[r + 1])):
+            if int(tree.mut_site[k]) in state:
+                assert state[int(tree.mut_site[k])] == tree.mut_from[k]
+                state[int(tree.mut_site[k])] = int(tree.mut_to[k])
+        hs.append(-float(tree.t[r])); root_C.append(sum(1 for l in state if state[l] == C_STATE))
+        if c % 500 == 0:          # the data stay: below the root's sequence, node 1 reaches C and node 2 reaches T at every one of the three sites
+            for node, want in ((1, C_STATE), (2, T_STATE)):
+                tip = dict(state)
+                for k in range(int(tree.mut_offset[node]), int(tree.mut_offset[node + 1])):
+                    if int(tree.mut_site[k]) in tip:
+                        tip[int(tree.mut_site[k])] = int(tree.mut_to[k])
+                assert all(v == want for v in tip.values()), (c, node, tip)
+    return np.array(hs), np.array(root_C, np.float64), ref, evo, sites
+
+
+def _check_apobec(hs, root_C, ref, evo, sites):
+    burn = len(hs) // 10
+    hs, root_C = hs[burn:], root_C[burn:]
+    want_h, want_share = _apobec_quadrature(ref, evo, sites)
+    assert abs(want_share - 0.8) < 1e-3 and 120.0 < want_h < 150.0, (want_share, want_h)      # (the first order, and Gamma(4, 1/N + 2 lambda)'s 134)
+    share, se = root_C.mean() / M_DIFF, _batch_se(root_C / M_DIFF)
+    print("root holds C at %.4f of the differing sites (se %.4f), quadrature %.5f; root height %.2f (se %.2f), quadrature %.2f" % (share, se, want_share, hs.mean(), _batch_se(hs), want_h))
+    assert 0.0 < se < 0.02, se                        # (the chain moves, and the check resolves 0.8 from 0.5 many times over)
+    assert abs(share - want_share) < 4.0 * se, "the root holds C at %.4f of the differing sites, quadrature %.5f (se %.4f; 0.5 without the asymmetry, 0.2 with q transposed)" % (share, want_share, se)
+    se_h = _batch_se(hs)
+    assert abs(hs.mean() - want_h) < 4.0 * se_h + 0.03 * want_h, "root height: mean %.2f, quadrature %.2f (se %.2f)" % (hs.mean(), want_h, se_h)
+
+
+def test_apobec_two_differing_tips_root_state_on_the_oracle():
+    orc = OracleEngine(L)
+    try:
+        out = _chain_apobec(orc, 43, CYCLES_APOBEC_ORACLE)
+    finally:
+        orc.close()
+    _check_apobec(*out)
+
+
+@pytest.mark.gpu
+def test_apobec_two_differing_tips_root_state_on_the_gpu():
+    gpu = d.EmatBackend(L)
+    try:
+        out = _chain_apobec(gpu, 47, 5000)
+    finally:
+        gpu.close()
+    _check_apobec(*out)

@@ -12,7 +12,7 @@ import mpox_moves_model as MM
 import skygrid_streams as RS
 from delphy_amd.engine import mpox_q_matrices
 from delphy_amd.scenarios import make_scenario
-from helpers import configure, split_parts
+from helpers import configure, replay_device_parts_in_the_oracle, split_parts
 from test_exact_model import Tally
 from test_mpox_run_host import apobec_partition, tip0_sequence
 
@@ -135,6 +135,35 @@ def test_five_whole_cycles_with_the_model_on(scenario, device_tree):
         run.reassemble()
         run.do_mcmc_steps(per_cycle, per_cycle)                            # ... and a cycle on it passes its checks
         assert run.hky()[0] == seen[-1][0]
+    finally:
+        run.close(); b.close()
+
+
+def test_three_cycles_move_for_move_against_the_oracle_under_the_models_the_device_drew(scenario):
+    """repartition(); mpox_moves(); then a pass of 3 x 600 + 7 local moves replayed in the oracle under the model the backend holds (get_evo) over the driver's
+    site partition; reassemble().  From the second cycle on mu* > 0: the matrices are those the device's own Gibbs rounds made."""
+    sc = scenario
+    b = d.EmatBackend(sc.num_sites, trace_moves=700)
+    run = d.EmatRun(b, sc.tree, sc.ref, SEED)
+    run.set_num_parts(3); run.set_hky(sc.mu, sc.kappa, sc.pi); run.set_pop_model(sc.pop); run.set_device_tree(True)
+    try:
+        run.set_mpox(True, SPEC)
+        ref, models = sc.ref, []
+        for k in range(3):
+            run.repartition()
+            run.mpox_moves()
+            mu, pi, q = b.get_evo()
+            pfs, count = run.mpox_partition()
+            m, m_star = run.mpox()
+            assert mu.tolist() == [m, m] and np.array_equal(q[1], mpox_q_matrices(m_star / m)[1]) and 0 < count < sc.num_sites
+            if k >= 1:
+                assert m_star > 0.0
+            models.append((m, m_star))
+            n = replay_device_parts_in_the_oracle(sc, b, run, ref, 3 * 600 + 7, 700, evo=(mu, pi, q, pfs))
+            assert n == 3
+            run.reassemble()
+            _, ref = run.tree()
+        assert len(set(models)) == 3
     finally:
         run.close(); b.close()
 

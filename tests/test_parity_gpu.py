@@ -139,6 +139,19 @@ def test_two_site_partitions():
     run_parity(sc, 3, 4000, seed=31, evo=(mu, pi, q, pfs))
 
 
+@pytest.mark.parametrize("use_lds", [True, False])
+@pytest.mark.parametrize("rho", [0.5, 20.0])
+def test_apobec_rate_matrices(rho, use_lds):
+    """The APOBEC (mpox) model's two partitions, cut by sequence context (tests/apobec_cases.py): Jukes-Cantor and q1 of rho under a flat pi, so that most
+    re-timings of a mutation have a log_mh of exactly 0, the Metropolis tie that is accepted without a uniform -- where the HKY cases of this file go only
+    with a branch that has no mutation.  A tie that came out on the other side of 0 on the device would draw an acceptance uniform the oracle did not, and
+    the chains would part."""
+    from apobec_cases import apobec_evo
+    sc = make_scenario("C1", num_tips=90, num_sites=6000)
+    st = run_parity(sc, 3, 4000, seed=31, trace=4000, use_lds=use_lds, evo=apobec_evo(sc, rho))
+    assert st["accepted"][2] > 0 and st["accepted"][3] + st["accepted"][4] > 0
+
+
 def test_skygrid_log_linear():
     sc = make_scenario("C3", num_tips=150, num_sites=5000, skygrid_log_linear=True)
     run_parity(sc, 4, 3000, seed=37)

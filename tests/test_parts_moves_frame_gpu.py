@@ -9,11 +9,10 @@ import numpy as np
 import pytest
 
 import delphy_amd as d
-from delphy_amd.engine import mpox_q_matrices
+from apobec_cases import apobec_evo
 from delphy_amd.scenarios import make_scenario
 from helpers import configure, split_parts
 from test_global_moves_frame_gpu import _answer, _bits
-from test_mpox_run_host import apobec_partition, tip0_sequence
 from test_tree_stages_gpu import _status
 
 pytestmark = pytest.mark.gpu
@@ -34,11 +33,8 @@ def cut(scenario):
 
 def _apobec_evo(sc, mu=None, pi=None, q=None):
     """(mu [2], pi [2][4], q [2][4][4], partition_for_site): the APOBEC model at rho = 0.5 over the scenario's tree, or the model given over the same two site partitions."""
-    pfs = apobec_partition(tip0_sequence(sc.tree, sc.ref)[0])
-    assert 0 < pfs.sum() < sc.num_sites
-    if mu is None:
-        mu, pi, q = np.array([sc.mu, sc.mu]), np.full((2, 4), 0.25), np.stack(mpox_q_matrices(0.5))
-    return mu, pi, q, pfs
+    model = apobec_evo(sc, 0.5)
+    return model if mu is None else (mu, pi, q, model[3])
 
 
 def _with_parts(sc, cut, evo=None):
